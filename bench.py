@@ -10,6 +10,10 @@ config 3 (16384 envs); --task binpick: config 5 shard (HandArm bin-picking: hard
 8192 envs/GPU). Multi-GPU: one process per GPU (torchrun), envs sharded, the only collective is the
 per-log-interval RCCL all-reduce of episode statistics.
 
+A plain run (no --full) sets up the one config asked for (--task all: the C2 headline), warms up, times the K
+steps, writes --dump-outputs if given and prints the line. --full adds everything else: the C3 / C4 / C5 / C4w
+sub-records of --task all, the CPU baselines and the whole-episode windows of the HandArm tasks.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
 import argparse
@@ -367,10 +371,68 @@ def compute_roofline(kernel, envs, kavg_ms, key=None):
             "source": "profiles/sq_{}{}.json".format(kernel, "_" + PROFILE_TAG[key] if key in PROFILE_TAG else "")}
 
 
-def run_config(task, envs, args, world, rank, device, log_interval_fn, key=None):
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000     # --dump-outputs: all files of one dump together
+DUMP_SAMPLE_SEED = 20240
+
+
+def _named_arrays(x, name, out):
+    """Flatten what VecTask.step() returned (tuple / dict nesting) into {dotted name: tensor or number}."""
+    if isinstance(x, dict):
+        for k in x:
+            _named_arrays(x[k], f"{name}.{k}" if name else str(k), out)
+    elif isinstance(x, (tuple, list)):
+        for i, v in enumerate(x):
+            _named_arrays(v, f"{name}.{i}" if name else str(i), out)
+    elif torch.is_tensor(x) or isinstance(x, (bool, int, float, np.number)):
+        out[name] = x
+
+
+def dump_outputs(ret, directory):
+    """Write what the last timed VecTask.step() returned - (obs_dict, rew, reset, extras) - as
+    <directory>/<name>.npy (obs.obs, rew, reset, extras.time_outs, ...): float32 for the float tensors, float64
+    for everything else (integer and bool buffers, Python numbers). An array over its share of the 64 MB budget is
+    cut to a seeded sample of its rows (the same rows every run).
+
+    Under i.i.d. random actions the physics of a single env now and then diverges (dof_state, root_state, rew and
+    rewards_episode turn NaN / inf) and stays so until its episode's timeout resets it: at 4096 envs, W = 5, env
+    1191 over timed steps 1580-1789. Such numbers cannot be compared between two builds, so an env with a
+    non-finite value in any per-env array has its rows written as zeros, and env_finite.npy (1 / 0 per env) says
+    which envs those are. Returns the number of such envs."""
+    named = {}
+    for top, part in zip(("obs", "rew", "reset", "extras"), ret):
+        _named_arrays(part, top, named)
+    arrays = {}
+    for name, v in named.items():
+        if torch.is_tensor(v):
+            t = v.detach().cpu()
+            narrow = t.is_floating_point() and t.dtype != torch.float64
+            a = t.to(torch.float32 if narrow else torch.float64).numpy().copy()
+        else:
+            a = np.asarray(v, np.float64)
+        arrays[name.replace("/", "_")] = a
+    n = int(ret[1].shape[0])                                    # rew: one value per env
+    per_env = [a for a in arrays.values() if a.ndim >= 1 and a.shape[0] == n]
+    finite = np.ones(n, bool)
+    for a in per_env:
+        finite &= np.isfinite(a.reshape(n, -1)).all(1)
+    for a in per_env:
+        a[~finite] = 0
+    arrays["env_finite"] = finite.astype(np.float64)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if a.nbytes > share and a.ndim >= 1 and a.shape[0] > 1:
+            rows = max(1, share // max(a[0].nbytes, 1))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.shape[0], rows, replace=False))
+            a = a[idx]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+    return int(n - finite.sum())
+
+
+def run_config(task, envs, args, world, rank, device, log_interval_fn, key=None, dump_dir=None):
     """Build the env, W warmup steps (the first includes the all-env reset and, for the HandArm tasks, drop
     init), then exactly K timed steps between barrier + synchronize pairs; returns the record (rank 0 gets the
-    max over ranks)."""
+    max over ranks). dump_dir: rank 0 writes the last timed step's return values there (dump_outputs)."""
     from handarm_hip import parallel
     seed = 42 + rank                  # utils/utils.py:94 (seed + rank)
     random.seed(seed)
@@ -397,8 +459,9 @@ def run_config(task, envs, args, world, rank, device, log_interval_fn, key=None)
         torch.distributed.barrier()
     t0 = time.perf_counter()
     ev[0].record()
+    ret = None
     for k in range(args.steps):
-        env.step(pool[k % len(pool)])
+        ret = env.step(pool[k % len(pool)])
         ev[k + 1].record()
         if (k + 1) % LOG_INTERVAL == 0:
             log_interval_fn(task, env)
@@ -410,6 +473,10 @@ def run_config(task, envs, args, world, rank, device, log_interval_fn, key=None)
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    dump_bad = None
+    if dump_dir and rank == 0 and ret is not None:
+        dump_bad = dump_outputs(ret, dump_dir)   # before anything else steps the env: the buffers are the task's own
+    del ret
     step_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.steps)]
     kern_ms = env.sim.kernel_times_ms(args.steps)
     pcs = getattr(env, "pointclouds", None)
@@ -440,6 +507,8 @@ def run_config(task, envs, args, world, rank, device, log_interval_fn, key=None)
         "compute_roofline": compute_roofline(kernel, envs, kavg, key),
         **extra,
     }
+    if dump_bad is not None:
+        rec["dump_non_finite_envs"] = dump_bad
     if pcs is not None:
         pb = pointcloud_bytes_per_env(pcs)
         pach = pb * envs / (statistics.mean(pc_ms) * 1e-3) / 1e9
@@ -447,7 +516,7 @@ def run_config(task, envs, args, world, rank, device, log_interval_fn, key=None)
                                       "kernel_avg_ms": statistics.mean(pc_ms), "algorithmic_bytes_per_env": pb,
                                       "achieved": pach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                       "frac": pach / HBM_PEAK_GBS}
-    if task in ("ur5sih", "binpick", "ur5sih_wide") and args.episode_steps > 0:
+    if args.full and task in ("ur5sih", "binpick", "ur5sih_wide") and args.episode_steps > 0:
         # the whole-episode window: the K-step window above starts right after the first reset, where
         # the arm has not reached the objects yet; the next episode_steps steps (one full 200-step episode, so one
         # synchronous reset step) give the steady-state rate and contact statistics north_star's figure is about
@@ -555,20 +624,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--task", choices=["all", "allegro_kuka", "ur5sih", "allegro_hand", "binpick", "ur5sih_wide"],
                     default="all",
-                    help="all (default): the C2 headline (allegro_kuka) plus sub-records for C3 (allegro_hand), "
-                         "C4 (ur5sih shard), C5 (binpick shard) and C4w (ur5sih shard on the 24-object pool); or one "
-                         "of them alone")
+                    help="all (default): the C2 headline (allegro_kuka), with --full plus sub-records for C3 "
+                         "(allegro_hand), C4 (ur5sih shard), C5 (binpick shard) and C4w (ur5sih shard on the 24-object "
+                         "pool); or one of them alone")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the sub-records of --task all, the CPU baselines "
+                         "(unless --no-cpu-baseline) and the whole-episode windows (--episode-steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the headline config returned "
+                         "(observations, rewards, resets, extras) as DIR/<name>.npy")
     ap.add_argument("--wide-pool", action="store_true", help="ur5sih / binpick: draw the objects from the 24-object "
                                                             "pool (the 8 concave objects as convex pieces)")
     ap.add_argument("--subtask", choices=["regrasping", "reorientation", "throw"], default="regrasping")
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU of a single --task (default: its config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU samples")
     ap.add_argument("--no-dr", action="store_true", help="ur5sih: domain randomization off")
     ap.add_argument("--pointclouds", action="store_true",
                     help="ur5sih / binpick: the point-cloud student observation list (synthetic clouds every step)")
     ap.add_argument("--episode-steps", type=int, default=200,
-                    help="ur5sih / binpick: also time this many steps after the K-step window (one whole 200-step "
-                         "episode incl. its synchronous reset step; 0: off)")
+                    help="--full, ur5sih / binpick: also time this many steps after the K-step window (one whole "
+                         "200-step episode incl. its synchronous reset step; 0: off)")
     ap.add_argument("--cpu-envs", type=int, default=1024)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU sample of the headline config")
     ap.add_argument("--cpu-seconds-sub", type=float, default=4.0, help="CPU sample of each sub-record")
@@ -595,7 +670,7 @@ def main():
         return parallel.reduce_episode_stats(env)            # RCCL all-reduce of the episode counters (N > 1)
 
     if args.task == "all":
-        head, subs = "C2", ["C3", "C4", "C5", "C4w"]
+        head, subs = "C2", (["C3", "C4", "C5", "C4w"] if args.full else [])
     else:
         head = next(k for k, v in CONFIGS.items() if v[0] == args.task)
         subs = []
@@ -604,8 +679,9 @@ def main():
         task, envs, _ = CONFIGS[key]
         if key == head and args.envs:
             envs = args.envs
-        records[key] = run_config(task, envs, args, world, rank, device, log_interval, key)
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+        records[key] = run_config(task, envs, args, world, rank, device, log_interval, key,
+                                  dump_dir=args.dump_outputs if key == head else None)
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         for key in [head] + subs:
             task = CONFIGS[key][0]
             records[key]["cpu_baseline"] = run_cpu_baseline(task, args, args.cpu_seconds if key == head
@@ -643,7 +719,7 @@ def main():
         "distributed": dist_info,
     }
     for k in ("episode_successes_mean", "consecutive_successes", "success_rate_ewma", "contacts", "pointcloud_roofline",
-              "episode_window"):
+              "episode_window", "dump_non_finite_envs"):
         if k in h:
             out[k] = h[k]
     if subs:

@@ -14,9 +14,9 @@ case $TASK in
   *) echo "unknown task $TASK"; exit 2 ;;
 esac
 P="cd /tmp && export TMPDIR=/tmp && rocprofv3"
-B="python3 $R/bench.py --task $TASK --steps 20 --warmup 5 --no-cpu-baseline"
+B="python3 $R/bench.py --full --task $TASK --steps 20 --warmup 5 --no-cpu-baseline"
 bash "$R/tools/gpu_round.sh" \
-  "bench|600|python $R/bench.py --task $TASK --cpu-seconds 6 > $O/${TAG}_bench${SFX}.json" \
+  "bench|600|python $R/bench.py --full --task $TASK --cpu-seconds 6 > $O/${TAG}_bench${SFX}.json" \
   "ks|400|$P --kernel-trace --stats --output-format csv -d $O/ks -- $B" \
   "ksx|60|cp $O/ks/*/*_kernel_stats.csv $O/${TAG}_bench${SFX}_kernel_stats.csv && rm -rf $O/ks" \
   "pmcf|400|$P --pmc FETCH_SIZE --output-format csv -d $O/pmcf -- $B" \

@@ -8,7 +8,7 @@ case $PART in
   a) bash tools/gpu_round.sh \
        "${TAG}_gpu_suite|600|python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread" \
        "${TAG}_smoke|300|python -u -c 'import __graft_entry__ as g; g.smoke()'" \
-       "${TAG}_bench_all|900|python -u bench.py > gpurun_out/${TAG}_bench_all.json" ;;
+       "${TAG}_bench_all|900|mkdir -p ${HA_OUT:-bench_out} && python -u bench.py --full > ${HA_OUT:-bench_out}/${TAG}_bench_all.json" ;;
   b) bash tools/profile_round.sh "$TAG" allegro_kuka && bash tools/profile_round.sh "$TAG" allegro_hand ;;
   c) bash tools/profile_round.sh "$TAG" ur5sih && bash tools/profile_round.sh "$TAG" binpick ;;
   d) bash tools/gpu_round.sh \
