@@ -95,6 +95,9 @@ HD float bcast(float x, int src) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), src));
 }
 HD int bcast_i(int x, int src) { return __builtin_amdgcn_readlane(x, src); }
+// value of lane `src` (per lane, 0..63; ds_bpermute_b32). A disabled source lane reads as 0: call it where the
+// source lanes are active
+HD int lane_read_i(int x, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, x); }
 
 // Reductions: DPP inside each 16-lane row (quad_perm xor1, xor2, row_half_mirror, row_mirror leave the
 // row's result in all 16 lanes), then across rows with row_bcast:15 (row 3 += row 2, row 1 += row 0) and

@@ -378,6 +378,8 @@ struct SimCtx {
     float* pcm;
     int pslot, pkind, pA, pB;
     int pemit;              // points of the running pair's manifold staged for its record (pcm_commit), 0: none
+    bool last;              // the launch's final substep (run_physics): the only one whose joint / contact forces
+                            // (PostScratch dforce, cforce) are read, so the only one that builds them
 #ifdef HA_PROFILE
     int pk;                 // profiled build: kind of the running pair
     int pcls;               // profiled build: this substep is heavy (g_prof's second set)
@@ -2504,15 +2506,23 @@ HD void detect(SimCtx& c) {
 // ----------------------------------------------------------------------------- constraint rows
 // Jacobian of body `body` into a compact row: robot block J (D wide; only touched for a link) and object
 // blocks Job (slot so0 -> 0, else 1; Job = J + D for a dense row)
+// the object part alone (body an object: 0 <= body < 100)
+HD void jac_obj(const SimCtx& c, int body, f3 x, f3 dir, float sgn, float* Job, int so0) {
+    if (body < 0 || body >= 100) return;
+    f3 r = x - ld3(c.o[body].oc);
+    f3 ang = cross3(r, dir);
+    float* Jo = Job + (body == so0 ? 0 : 6);
+    Jo[0] += sgn * dir.x; Jo[1] += sgn * dir.y; Jo[2] += sgn * dir.z;
+    Jo[3] += sgn * ang.x; Jo[4] += sgn * ang.y; Jo[5] += sgn * ang.z;
+}
+// The robot part walks the link tree through the model (two dependent global loads and a read-modify-write of J per
+// hop). The rows phase now takes each link's ancestor DOFs from a per-lane bit mask instead (substep, link_dof_masks);
+// HA_X_JAC_WALK builds keep this walk for A/B timing.
 HD void jac_body(const SimCtx& c, int body, f3 x, f3 dir, float sgn, float* J, float* Job, int so0) {
     const EnvLDS& s = *c.s;
     if (body < 0) return;
     if (body < 100) {
-        f3 r = x - ld3(c.o[body].oc);
-        f3 ang = cross3(r, dir);
-        float* Jo = Job + (body == so0 ? 0 : 6);
-        Jo[0] += sgn * dir.x; Jo[1] += sgn * dir.y; Jo[2] += sgn * dir.z;
-        Jo[3] += sgn * ang.x; Jo[4] += sgn * ang.y; Jo[5] += sgn * ang.z;
+        jac_obj(c, body, x, dir, sgn, Job, so0);
         return;
     }
     for (int j = body - 100; j >= 0; j = c.m->link_parent[j]) {
@@ -2520,6 +2530,31 @@ HD void jac_body(const SimCtx& c, int body, f3 x, f3 dir, float sgn, float* J, f
         if (d < 0) continue;
         J[d] += sgn * dot3(ld3(s.ax[d]), cross3(x - ld3(s.an[d]), dir));
     }
+}
+
+// Lane = link: the DOFs on the link's path to the root (its own included), a bit each. One coalesced load of the
+// link's parent and DOF, then pointer jumping in registers: after round k a lane holds the DOFs of its 2^k nearest
+// ancestors-or-self and `par` is the link 2^k above (-1: past the root), so five rounds cover any tree of
+// HA_MAX_LINKS links. Needs every lane active (ds_bpermute reads 0 from a disabled lane).
+HD uint32_t link_dof_masks(const SimCtx& c) {
+    static_assert(HA_MAX_LINKS <= 32 && HA_MAX_DOFS <= 32, "five jumps; a 32-bit DOF mask");
+    int lane = c.lane, par = -1, d = -1;
+    if (lane < c.L) {
+        par = c.m->link_parent[lane];
+        d = c.m->link_dof[lane];
+    }
+    uint32_t am = d >= 0 ? 1u << d : 0u;
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        int src = par < 0 ? lane : par;
+        uint32_t pm = (uint32_t)lane_read_i((int)am, src);
+        int pp = lane_read_i(par, src);
+        if (par >= 0) {
+            am |= pm;
+            par = pp;
+        }
+    }
+    return am;
 }
 
 HD void tangents(f3 n, f3& t1, f3& t2) {
@@ -2732,10 +2767,28 @@ HD void substep(SimCtx& c, float hdt) {
     float* PK = PC::pack ? reinterpret_cast<float*>(reinterpret_cast<char*>(s.u.rows.J) + pc_pk_offset<PC>()) : nullptr;
     // chunk ch's rows. LDS (true) / global (false) dense rows are separate instantiations, so that no pointer may
     // address both (a flat pointer would make chunk 0's LDS rows flat accesses too)
+#ifndef HA_X_JAC_WALK
+    // robot blocks without the link tree in memory: lane = link holds the link's ancestor DOFs (link_dof_masks), a row
+    // lane takes the masks of its two bodies across lanes and evaluates the set DOFs in registers
+    const uint32_t am = link_dof_masks(c);
+#endif
     auto rows_chunk = [&](int ch, auto lds_tag) {
         constexpr bool LDSROWS = decltype(lds_tag)::value;
         float vt_ = 0.f, winv_ = 0.f, cmu_ = 0.f;
         int r = RPC * ch + lane;
+#ifndef HA_X_JAC_WALK
+        // the DOF masks of the row's bodies a and b (0: no link). Before the row lanes diverge: the cross-lane read sees
+        // active lanes only
+        uint32_t ma = 0u, mb = 0u;
+        {
+            int a_ = -1, b_ = -1;
+            if (lane < RPC && r < nr) ct_ab(c, r / 3, a_, b_);
+            uint32_t xa = (uint32_t)lane_read_i((int)am, a_ >= 100 ? a_ - 100 : 0);
+            uint32_t xb = (uint32_t)lane_read_i((int)am, b_ >= 100 ? b_ - 100 : 0);
+            ma = a_ >= 100 ? xa : 0u;
+            mb = b_ >= 100 ? xb : 0u;
+        }
+#endif
         if (lane < RPC && r < nr) {
             const ContactLDS ct = ct_get(c, r / 3);
             cmu_ = contact_friction(c, ct.a, ct.b);
@@ -2743,8 +2796,9 @@ HD void substep(SimCtx& c, float hdt) {
             // robot block Jr / Yr (null: the contact touches no link, the block is zero) and object blocks Jo / Yo
             float *Jr, *Yr, *Jo, *Yo;
             float jo_rc[PC::rc ? OW : 1], yo_rc[PC::rc ? OW : 1];     // RC: this row's object blocks, in registers
+            int ls = -1;                                              // split rows: the contact's link slot
             if constexpr (PC::split) {
-                int ls = lslot(r / 3);
+                ls = lslot(r / 3);
                 Jr = ls >= 0 ? rrow(ls, k, false) : nullptr;
                 Yr = ls >= 0 ? rrow(ls, k, true) : nullptr;
                 if constexpr (PC::rc) {
@@ -2760,8 +2814,10 @@ HD void substep(SimCtx& c, float hdt) {
                     }
                     for (int t = 0; t < OW; t++) Jo[t] = 0.0f;
                 }
+#ifdef HA_X_JAC_WALK
                 if (Jr)
                     for (int t = 0; t < ND; t++) Jr[t] = 0.0f;
+#endif
             } else {
                 if constexpr (LDSROWS) {
                     Jr = Jb + r * RSN;
@@ -2772,7 +2828,11 @@ HD void substep(SimCtx& c, float hdt) {
                 }
                 Jo = Jr + D;
                 Yo = Yr + D;
+#ifdef HA_X_JAC_WALK
                 for (int t = 0; t < RSN; t++) Jr[t] = 0.0f;
+#else
+                for (int t = 0; t < RSN - ND; t++) Jo[t] = 0.0f;    // the robot block is stored whole below (D = ND)
+#endif
             }
             f3 n = ld3(ct.n), t1, t2;
             tangents(n, t1, t2);
@@ -2780,6 +2840,7 @@ HD void substep(SimCtx& c, float hdt) {
             f3 x = ld3(ct.x);
             int so0, so1;
             contact_slots(ct.a, ct.b, so0, so1);
+#ifdef HA_X_JAC_WALK
             if constexpr (PC::rc) {
                 // robot block from the link bodies; both object blocks (and their Y) straight into registers
                 if (ct.a >= 100) jac_body(c, ct.a, x, dir, 1.0f, Jr, nullptr, so0);
@@ -2790,6 +2851,45 @@ HD void substep(SimCtx& c, float hdt) {
                 jac_body(c, ct.a, x, dir, 1.0f, Jr, Jo, so0);
                 jac_body(c, ct.b, x, dir, -1.0f, Jr, Jo, so0);
             }
+#else
+            // robot block: entry d is 0, + the a-term if d moves body a, then + the b-term if it moves body b (jac_body's
+            // sums in its order), summed in a register and stored once. LDS slots / rows and global rows keep their own
+            // store paths (no pointer that may address both)
+            const bool rl = PC::split ? ls < KL : LDSROWS;      // the robot block is in LDS (else: a global row)
+            HA_AS_LDS float *JrL, *YrL;                         // only the pair that rl selects is dereferenced
+            HA_AS_GLB float *JrG, *YrG;
+            if constexpr (PC::split) {
+                JrL = (HA_AS_LDS float*)(Rb + (3 * ls + k) * ND);
+                YrL = (HA_AS_LDS float*)(RbY + (3 * ls + k) * ND);
+                JrG = (HA_AS_GLB float*)(c.spill + (3 * (ls - KL) + k) * ND);
+                YrG = JrG + SPJ;
+            } else {
+                JrL = (HA_AS_LDS float*)Jr; YrL = (HA_AS_LDS float*)Yr;
+                JrG = (HA_AS_GLB float*)Jr; YrG = (HA_AS_GLB float*)Yr;
+            }
+            if (Jr) {
+                // (a rolled loop: unrolled, its 6 x ND LDS loads are scheduled together and spill)
+#pragma unroll 1
+                for (int d = 0; d < ND; d++) {
+                    float v = 0.0f;
+                    if (((ma | mb) >> d) & 1u) {
+                        float t = dot3(ld3(s.ax[d]), cross3(x - ld3(s.an[d]), dir));
+                        if ((ma >> d) & 1u) v += 1.0f * t;
+                        if ((mb >> d) & 1u) v += -1.0f * t;
+                    }
+                    if (rl) JrL[d] = v;
+                    else JrG[d] = v;
+                }
+            }
+            if constexpr (PC::rc) {
+                // both object blocks (and their Y) straight into registers
+                obj_block(c, so0, ct.a, x, dir, jo_rc, yo_rc);
+                obj_block(c, so1, ct.a, x, dir, jo_rc + 6, yo_rc + 6);
+            } else {
+                jac_obj(c, ct.a, x, dir, 1.0f, Jo, so0);
+                jac_obj(c, ct.b, x, dir, -1.0f, Jo, so0);
+            }
+#endif
             if (k == 0) {
                 float sp = ct.sep;
                 float sb = sp + p.contact_slop < 0.0f ? sp + p.contact_slop : 0.0f;   // penetration beyond the slop
@@ -2798,20 +2898,46 @@ HD void substep(SimCtx& c, float hdt) {
                 vt_ = v0;
             }
             // Y_r = M^-1 J_r^T (robot block through the explicit inverse, object blocks 1/m, I_w^-1). The robot terms of
-            // J_r . Y_r (the dense row's first terms, in its order) accumulate here from registers, so the block is
-            // not read back: Jr / Yr may be a global spill row (a generic pointer, flat accesses)
+            // J_r . Y_r (the dense row's first terms, in its order) accumulate here, so Y_r is not read back. An LDS slot /
+            // row and a global (spill / overflow) row keep their own typed accesses (HA_X_JAC_WALK: one generic pointer)
             float a = 0.0f;
             if (Jr) {
+#ifdef HA_X_JAC_WALK
                 // J_r to registers first: read once here instead of D times in the product loop (same sums, same order)
                 float jr[ND];
 #pragma unroll
                 for (int j = 0; j < ND; j++) jr[j] = Jr[j];
+#else
+                // (read back, not kept from the loop over d above: written at a running index the array would live in
+                // scratch)
+                float jr[ND];
+                if (rl) {
+#pragma unroll
+                    for (int j = 0; j < ND; j++) jr[j] = JrL[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j < ND; j++) jr[j] = JrG[j];
+                }
+#endif
                 for (int i = 0; i < D; i++) {
                     float acc = 0.0f;
 #pragma unroll
                     for (int j = 0; j < ND; j++) acc = fmaf(c.Minv[i * D + j], jr[j], acc);
+#ifdef HA_X_JAC_WALK
                     Yr[i] = acc;
                     a = fmaf(jr[i], acc, a);
+#else
+                    // J_r[i] from the row again (the same value): jr stays statically indexed, in registers
+                    float ji;
+                    if (rl) {
+                        YrL[i] = acc;
+                        ji = JrL[i];
+                    } else {
+                        YrG[i] = acc;
+                        ji = JrG[i];
+                    }
+                    a = fmaf(ji, acc, a);
+#endif
                 }
             }
             for (int sl = 0; sl < (PC::rc ? 0 : row_slots<ND>()); sl++) {    // RC: Y already from obj_block
@@ -2848,6 +2974,9 @@ HD void substep(SimCtx& c, float hdt) {
             rk(0, r) = 0.0f; rk(1, r) = vt_; rk(2, r) = winv_; rk(3, r) = cmu_;
         }
     };
+#ifdef HA_AB_ROWS_TWICE     /* A/B timing builds only: the rows phase (rows, then Delassus entries) run twice */
+    for (int rep = 0; rep < 2; rep++)
+#endif
 #pragma unroll 1
     for (int ch = 0; ch < NCH; ch++) {
         if (NCH > 1 && RPC * ch >= nr && (PC::ovf || ch > 0)) break;      // wave-uniform: no rows left
@@ -2934,6 +3063,9 @@ HD void substep(SimCtx& c, float hdt) {
             rk(4, r) = ca0_; rk(5, r) = ca1_;
         }
     };
+#ifdef HA_AB_ROWS_TWICE
+    for (int rep = 0; rep < 2; rep++)
+#endif
 #pragma unroll 1
     for (int ch = 0; ch < NCH; ch++) {
         if (NCH > 1 && RPC * ch >= nr && (PC::ovf || ch > 0)) break;
@@ -3034,6 +3166,15 @@ HD void substep(SimCtx& c, float hdt) {
     //      contact rows r = 0..nr-1.  Same row order and arithmetic as the oracle.
     const float* J = Jb;
     const float* Y = Yb;
+#ifndef HA_X_PGS_FETCH_GENERIC
+    // split rows: lane i keeps the link slot of contact i (and of contact 64 + i), -1: no link, so the sweeps read a
+    // contact's slot from a register instead of counting mask bits at every fetch
+    int lsl0 = -1, lsl1 = -1;
+    if constexpr (PC::split && !PC::rc) {
+        lsl0 = lslot(lane);
+        if (CAP * NCH > 64) lsl1 = lslot(lane + 64);
+    }
+#endif
     // several chunks: the row constants of the chunk after the current one, loaded while the current one is solved
     float sl = 0.f, svt = 0.f, swinv = 0.f, scmu = 0.f, sca0 = 0.f, sca1 = 0.f;
     auto stage = [&](int ch) {
@@ -3101,7 +3242,11 @@ HD void substep(SimCtx& c, float hdt) {
         float h0n = 0.f, h1n = 0.f, h2n = 0.f, g0n = 0.f, g1n = 0.f, g2n = 0.f;   // coordinate 64 + lane
         float j0m = 0.f, j1m = 0.f, j2m = 0.f, y0m = 0.f, y1m = 0.f, y2m = 0.f;
         float h0m = 0.f, h1m = 0.f, h2m = 0.f, g0m = 0.f, g1m = 0.f, g2m = 0.f;
+#ifdef HA_X_PGS_FETCH_GENERIC   /* A/B: the slot by shift and popcount per fetch, generic pointers for AllegroKuka */
         constexpr bool TF = !PC::minv_in_union;        // typed fetch paths (lds_f), except the compact AllegroKuka layout
+#else
+        constexpr bool TF = true;                      // typed fetch paths (lds_f / glb_f) in every family
+#endif
         auto fetch = [&](int ci) {
             float &j0n = j0m, &j1n = j1m, &j2n = j2m, &y0n = y0m, &y1n = y1m, &y2n = y2m;
             float &h0n = h0m, &h1n = h1m, &h2n = h2m, &g0n = g0m, &g1n = g1m, &g2n = g2m;
@@ -3160,8 +3305,30 @@ HD void substep(SimCtx& c, float hdt) {
                 // object coordinates from the object blocks (LDS for chunks < LCH, else the env's global row area);
                 // robot coordinates from the contact's link slot (LDS for the first KL, else the global spill rows),
                 // absent -> 0. LDS and global sources stay on separate paths (both conditions are wave-uniform)
+#ifdef HA_X_PGS_FETCH_GENERIC
                 int lsc = lslot(ci);
+#else
+                // the contact's link slot from the lane that holds it (one v_readlane: ci is wave-uniform)
+                int lsc = (CAP * NCH <= 64 || ci < 64) ? bcast_i(lsl0, ci) : bcast_i(lsl1, ci - 64);
+#endif
                 bool lds_obj = LCH == NCH || ci < CAP * LCH;
+#ifndef HA_X_PGS_FETCH_GENERIC
+                if (lds_obj && lsc < KL) {
+                    // every entry of this contact is in LDS: one set of six LDS loads from one base (the rows' J), each
+                    // lane's block (object block of contact ci at stride OW, or robot block of slot lsc at stride ND)
+                    // chosen by offsets. With one object slot ix is the lane's own, so everything here but the
+                    // (ci | lsc) multiple is invariant over the contacts and the sweeps
+                    constexpr int oOY = RPC * LCH * OW, oR = 2 * oOY, oRY = oR + 3 * KL * ND;   // ObY, Rb, RbY from Ob
+                    bool ob = ix >= D, rb = ix >= 0 && ix < D && lsc >= 0;
+                    int o0 = ob ? ix - D : oR + ix;
+                    int st = ob ? OW : ND;
+                    int dy = ob ? oOY : oRY - oR;
+                    if (ob || rb) {
+                        const HA_AS_LDS float* P = (const HA_AS_LDS float*)Ob + (o0 + 3 * st * (ob ? ci : lsc));
+                        j0n = P[0]; j1n = P[st]; j2n = P[2 * st];
+                        y0n = P[dy]; y1n = P[dy + st]; y2n = P[dy + 2 * st];
+                    }
+#else
                 if (lds_obj && lsc < KL) {
                     // every entry of this contact is in LDS: one set of loads, each lane's block (object block at
                     // stride OW, or the link slot's robot block at stride ND) chosen per lane
@@ -3175,6 +3342,7 @@ HD void substep(SimCtx& c, float hdt) {
                         j0n = P[0]; j1n = P[st]; j2n = P[2 * st];
                         y0n = PY[0]; y1n = PY[st]; y2n = PY[2 * st];
                     }
+#endif
                 } else if (ix >= D) {
                     int t = ix - D;
                     auto ldo = [&](auto On, auto OYn) {
@@ -3394,8 +3562,16 @@ HD void substep(SimCtx& c, float hdt) {
         }
         }
     }
+    // Joint and contact forces: the last substep wins, like the oracle, and nothing reads them before the launch's
+    // final substep has run (PostScratch), so only that substep builds them (wave-uniform)
+#ifdef HA_X_FORCES_EVERY_SUBSTEP    /* A/B: every substep, the contact forces by lane 0 alone */
+    const bool forces = true;
+#else
+    const bool forces = c.last;
+#endif
     // impulse of global row RPC ch + lane (xfer sits before RK / PK in the union: no overlap)
-    if (packed) {
+    if (!forces) {
+    } else if (packed) {
         for (int r = lane; r < nr; r += 64) s.u.xfer[r] = ((HA_AS_LDS float*)PK)[HA_PK * (r / 3) + r % 3];
     } else if (!multi) {
         if (lane < RPC) s.u.xfer[lane] = klam;
@@ -3404,12 +3580,39 @@ HD void substep(SimCtx& c, float hdt) {
         for (int ch = 0; ch < NCH; ch++)
             if (lane < RPC && CAP * ch < nc) s.u.xfer[RPC * ch + lane] = rk(0, RPC * ch + lane);
     }
-    if (lane < D) s.u.pd.dforce[lane] = (((dlam + lam_lo) - lam_up) + lam_fr) / hdt;
+    if (forces && lane < D) s.u.pd.dforce[lane] = (((dlam + lam_lo) - lam_up) + lam_fr) / hdt;
     wsync();
     if (lane < NV) s.v[lane] = vreg;
     if (VW == 2 && lane + 64 < NV) s.v[lane + 64] = vregh;
     PROF(6);
-    // contact forces (last substep wins, like the oracle)
+#ifndef HA_X_FORCES_EVERY_SUBSTEP
+    if (forces) {
+        // each contact's force by a lane of its own, in place over the contact's three impulses
+        for (int ci = lane; ci < nc; ci += 64) {
+            int r0 = 3 * ci;
+            const ContactLDS ct = ct_get(c, ci);
+            f3 n = ld3(ct.n), t1, t2;
+            tangents(n, t1, t2);
+            f3 f = (n * s.u.xfer[r0] + t1 * s.u.xfer[r0 + 1]) + t2 * s.u.xfer[r0 + 2];
+            f = f * (1.0f / hdt);
+            st3(&s.u.xfer[r0], f);
+        }
+        wsync();
+        // lane = body: its sum runs over the contacts in index order, side a (+) before side b (-), from 0: the
+        // order in which the oracle adds into the body's row
+        f3 acc = mk3(0.f, 0.f, 0.f);
+        for (int ci = 0; ci < nc; ci++) {
+            int ba, bb;
+            ct_ab(c, ci, ba, bb);
+            f3 f = ld3(&s.u.xfer[3 * ci]);
+            int ia = ba >= 100 ? m.body_robot0 + (ba - 100) : (ba >= 0 ? m.body_object0 + ba : -1);
+            int ib = bb >= 100 ? m.body_robot0 + (bb - 100) : (bb >= 0 ? m.body_object0 + bb : -1);
+            if (ia == lane) { acc.x += 1.0f * f.x; acc.y += 1.0f * f.y; acc.z += 1.0f * f.z; }
+            if (ib == lane) { acc.x += -1.0f * f.x; acc.y += -1.0f * f.y; acc.z += -1.0f * f.z; }
+        }
+        if (lane < MAXB) st3(s.u.pd.cforce[lane], acc);
+    }
+#else
     if (lane == 0) {
         for (int b = 0; b < MAXB; b++) s.u.pd.cforce[b][0] = s.u.pd.cforce[b][1] = s.u.pd.cforce[b][2] = 0.f;
         for (int ci = 0; ci < nc; ci++) {
@@ -3431,6 +3634,8 @@ HD void substep(SimCtx& c, float hdt) {
             }
         }
     }
+#endif
+    static_assert(MAXB <= 64, "contact forces: a lane per body");
     wsync();
     // ---- integrate
     if (lane < D) {

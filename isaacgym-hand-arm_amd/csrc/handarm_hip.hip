@@ -367,7 +367,10 @@ template <class PC>
 __device__ __forceinline__ void run_physics(SimCtx& c, int n_calls) {
     float hdt = c.p->dt / (float)c.p->substeps;
     for (int k = 0; k < n_calls; k++) {
-        for (int sub = 0; sub < c.p->substeps; sub++) substep<PC>(c, hdt);
+        for (int sub = 0; sub < c.p->substeps; sub++) {
+            c.last = k == n_calls - 1 && sub == c.p->substeps - 1;
+            substep<PC>(c, hdt);
+        }
         if (c.lane < c.NO) {
             c.o[c.lane].ofx[0] = c.o[c.lane].ofx[1] = c.o[c.lane].ofx[2] = 0.0f;
             c.o[c.lane].otq[0] = c.o[c.lane].otq[1] = c.o[c.lane].otq[2] = 0.0f;
