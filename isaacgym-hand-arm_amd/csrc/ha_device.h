@@ -118,11 +118,23 @@ HD float dpp_row_f(float old, float x) {
 template <int CTRL, int RM>
 HD int dpp_row_i(int old, int x) { return __builtin_amdgcn_update_dpp(old, x, CTRL, RM, 0xF, false); }
 HD float lane63(float x) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63)); }
+// one cross-row step of a sum whose only reader is lane 63: x + (x moved by CTRL in the rows of RM). The lanes outside
+// the row mask get an undefined addend, so the step is two instructions (a defined `old` costs a third, the v_mov that
+// sets it). Lane 63 never sees an undefined lane: its row is enabled in both steps, and the lane 31 it takes in the
+// second step was enabled in the first. -DHA_X_ROWSUM_ZERO_OLD (A/B): old = 0, the three-instruction step
+template <int CTRL, int RM>
+HD float dpp_row_add(float x) {
+#ifdef HA_X_ROWSUM_ZERO_OLD
+    return x + dpp_row_f<CTRL, RM>(0.0f, x);
+#else
+    return x + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, RM, 0xF, false));
+#endif
+}
 
 // sum of the four row results: (r3 + r2) + (r1 + r0) in lane 63
 HD float rows_sum(float x) {
-    x = x + dpp_row_f<0x142, 0xA>(0.0f, x);
-    x = x + dpp_row_f<0x143, 0xC>(0.0f, x);
+    x = dpp_row_add<0x142, 0xA>(x);
+    x = dpp_row_add<0x143, 0xC>(x);
     return lane63(x);
 }
 HD float wave_max(float x) {

@@ -510,8 +510,8 @@ HD void wave_sum_rows3(float& a, float& b, float& c) {
     a += dpp_f<0x4E>(a); b += dpp_f<0x4E>(b); c += dpp_f<0x4E>(c);
     a += dpp_f<0x141>(a); b += dpp_f<0x141>(b); c += dpp_f<0x141>(c);
     a += dpp_f<0x140>(a); b += dpp_f<0x140>(b); c += dpp_f<0x140>(c);
-    a = a + dpp_row_f<0x142, 0xA>(0.0f, a); b = b + dpp_row_f<0x142, 0xA>(0.0f, b); c = c + dpp_row_f<0x142, 0xA>(0.0f, c);
-    a = a + dpp_row_f<0x143, 0xC>(0.0f, a); b = b + dpp_row_f<0x143, 0xC>(0.0f, b); c = c + dpp_row_f<0x143, 0xC>(0.0f, c);
+    a = dpp_row_add<0x142, 0xA>(a); b = dpp_row_add<0x142, 0xA>(b); c = dpp_row_add<0x142, 0xA>(c);
+    a = dpp_row_add<0x143, 0xC>(a); b = dpp_row_add<0x143, 0xC>(b); c = dpp_row_add<0x143, 0xC>(c);
     a = lane63(a); b = lane63(b); c = lane63(c);
 }
 // three 16-lane row sums (the first four steps of wave_sum_rows3): every lane of a row gets its row's
@@ -2598,7 +2598,9 @@ HD void obj_entry(const SimCtx& c, int o, int a, f3 x, f3 dir, int t, float& j, 
 }
 
 
-template <class PC>
+// SETS3: the PGS contact loop with its row entries in three register sets that rotate by name (below); a kernel that
+// would pay for them in scratch passes false and keeps the copy loop
+template <class PC, bool SETS3 = true>
 HD void substep(SimCtx& c, float hdt) {
     constexpr int ND = PC::nd, NCH = PC::nch, VW = PC::vw;
     constexpr int RSN = row_stride<ND>();
@@ -3184,6 +3186,59 @@ HD void substep(SimCtx& c, float hdt) {
     };
     if (!packed && multi && lane < RPC) stage(0);
     const int nca = (nc + CAP - 1) / CAP;                   // chunks in use (wave-uniform)
+    // the Ur5Sih 3-object family (two row slots, one velocity word): ha_step_kernel sits at its 168 VGPRs with 64
+    // B/lane of scratch and the three row sets put it at 72, so it keeps the copy loop
+    constexpr bool HA3 = row_slots<ND>() == 2 && VW == 1;
+    // joint rows: row d + 1 of S ~ M^-1 is loaded before row d's chain runs (the next sweep's row 0 at d = D - 1), so its
+    // LDS latency passes under a whole joint's work. Only the clutter family (two velocity words) has it: its kernel
+    // measured 2.9% faster with it, the AllegroHand kernel 1.1% slower, AllegroKuka nothing, and ha_step_kernel pays
+    // for the register in scratch (profiles/r08_pgs_sweep.txt). -DHA_X_JOINT_ROW_NO_PREFETCH (A/B): no family
+#ifdef HA_X_JOINT_ROW_NO_PREFETCH
+    constexpr bool JP = false;
+#else
+    constexpr bool JP = VW == 2;
+#endif
+    float mnext = JP && lane < D ? c.Minv[lane] : 0.0f;
+    // contact blocks: the row entries of a contact live in one of three register sets that rotate by name. The contact
+    // loop is unrolled by three, copy k reads set k and prefetches (two contacts ahead) into the set copy k - 1 has
+    // just finished with, so no set is ever copied and the loads go straight into the registers a block reads (the
+    // waits the conditional fetch paths still leave: profiles/r08_pgs_sweep.txt, section 4).
+    // (-DHA_X_PGS_ROTATE_COPIES, A/B: two sets and the current one rotated by register copies, which wait for the
+    // look-ahead loads one block after their issue, and a zero-fill of the set before every fetch)
+    struct RowSet {
+        float j0 = 0.f, j1 = 0.f, j2 = 0.f, y0 = 0.f, y1 = 0.f, y2 = 0.f;
+        float h0 = 0.f, h1 = 0.f, h2 = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f;      // coordinate 64 + lane
+    };
+#ifdef HA_X_PGS_ROTATE_COPIES
+    constexpr bool ROT = false;
+#else
+    // the rotation restarts with every chunk, so a chunk holds whole trips; the two-word family (VW == 2, the clutter
+    // kernels at their 168-VGPR cap) would keep 36 row registers in three sets and stays on the copy loop
+    constexpr bool ROT = SETS3 && VW == 1 && CAP % 3 == 0 && !HA3;
+#endif
+    // One row slot and split rows (AllegroKuka): a lane's compact index is its own for every contact, so everything
+    // per lane in a fetch is fixed here, once per substep: whether it reads an object or a robot block, its offset
+    // within the first such block in LDS (from Ob) and in the env's global area (from c.spill), the blocks' row stride
+    // and the distance from a J entry to its Y entry. A fetch adds the contact's wave-uniform block offset and issues
+    // one set of LDS loads and one of global loads, each under its own lane mask. The lanes that never have an entry
+    // keep the 0 their sets start each sweep with; only the robot lanes of a contact without a link are zeroed, for
+    // that contact alone. Dense rows with one row slot (AllegroHand) need no zero either: the same lanes load for every
+    // contact. The other families zero-fill the set before every fetch, as the copy loop does (it makes every lane
+    // wait for the set's previous loads)
+#ifdef HA_X_PGS_FETCH_GENERIC
+    constexpr bool UF = false;
+#else
+    constexpr bool UF = ROT && PC::split && !PC::rc && row_slots<ND>() == 1;
+#endif
+    constexpr bool NZF = UF || (ROT && !PC::split && row_slots<ND>() == 1);
+    // (all in bytes, 32 bits: an LDS address is one, and a global load takes the scalar base with a 32-bit lane offset)
+    const bool f_ob = UF && lane >= D && lane < RSN, f_rb = UF && lane < D;
+    constexpr uint32_t f_oOY = RPC * LCH * OW, f_oR = 2 * f_oOY, f_oRY = f_oR + 3 * KL * ND;   // ObY, Rb, RbY from Ob
+    const uint32_t f_obm = f_ob ? ~0u : 0u;
+    const uint32_t f_st = 4u * (f_ob ? OW : ND);
+    const uint32_t f_lo = 4u * (f_ob ? lane - D : f_oR + lane), f_ly = 4u * (f_ob ? f_oOY : f_oRY - f_oR);
+    const uint32_t f_go = 4u * (f_ob ? PC::spill_robot - RPC * LCH * OW + (lane - D) : lane);
+    const uint32_t f_gy = 4u * (f_ob ? RPC * (NCH - LCH) * OW : SPJ);
 #ifdef HA_AB_PGS_TWICE
     for (int it = 0; it < 2 * p.solver_iters; it++) {
 #else
@@ -3193,7 +3248,13 @@ HD void substep(SimCtx& c, float hdt) {
         // constants: the same operands the oracle uses), and only the impulse change crosses lanes (one
         // v_readlane); the joint-limit rows run only for the joints whose limit is active (ballot masks).
         for (int d = 0; d < D; d++) {
-            float mrow = lane < D ? c.Minv[d * D + lane] : 0.0f;
+            float mrow;
+            if constexpr (JP) {
+                mrow = mnext;
+                mnext = lane < D ? c.Minv[(d + 1 < D ? d + 1 : 0) * D + lane] : 0.0f;
+            } else {
+                mrow = lane < D ? c.Minv[d * D + lane] : 0.0f;
+            }
             float nl = dlam - (vreg + dbias + dgam * dlam) * dwinv;
             nl = nl < -dlim ? -dlim : (nl > dlim ? dlim : nl);
             float dl = bcast(nl - dlam, d);
@@ -3234,22 +3295,17 @@ HD void substep(SimCtx& c, float hdt) {
         // normal (and first friction) update through the block's Delassus entries, which equals
         // re-reducing J.v after each row (row-by-row Gauss-Seidel) up to rounding
         // lane = generalized coordinate; its entry of a compact row is at compact_index (or absent -> 0).
-        // The next contact's row entries are prefetched while the current one reduces.
-        // (two contacts ahead: the m set is filled by fetch, the n set is the next contact's; an overflow chunk's rows
-        // and most link contacts' robot blocks come from the env's global area, whose latency one contact of
-        // reductions does not cover)
-        float j0n = 0.f, j1n = 0.f, j2n = 0.f, y0n = 0.f, y1n = 0.f, y2n = 0.f;
-        float h0n = 0.f, h1n = 0.f, h2n = 0.f, g0n = 0.f, g1n = 0.f, g2n = 0.f;   // coordinate 64 + lane
-        float j0m = 0.f, j1m = 0.f, j2m = 0.f, y0m = 0.f, y1m = 0.f, y2m = 0.f;
-        float h0m = 0.f, h1m = 0.f, h2m = 0.f, g0m = 0.f, g1m = 0.f, g2m = 0.f;
+        // The row entries of the contact two ahead are prefetched while the current one reduces (an overflow chunk's
+        // rows and most link contacts' robot blocks come from the env's global area, whose latency one contact of
+        // reductions does not cover).
 #ifdef HA_X_PGS_FETCH_GENERIC   /* A/B: the slot by shift and popcount per fetch, generic pointers for AllegroKuka */
         constexpr bool TF = !PC::minv_in_union;        // typed fetch paths (lds_f), except the compact AllegroKuka layout
 #else
         constexpr bool TF = true;                      // typed fetch paths (lds_f / glb_f) in every family
 #endif
-        auto fetch = [&](int ci) {
-            float &j0n = j0m, &j1n = j1m, &j2n = j2m, &y0n = y0m, &y1n = y1m, &y2n = y2m;
-            float &h0n = h0m, &h1n = h1m, &h2n = h2m, &g0n = g0m, &g1n = g1m, &g2n = g2m;
+        auto fetch = [&](int ci, RowSet& S) {
+            float &j0n = S.j0, &j1n = S.j1, &j2n = S.j2, &y0n = S.y0, &y1n = S.y1, &y2n = S.y2;
+            float &h0n = S.h0, &h1n = S.h1, &h2n = S.h2, &g0n = S.g0, &g1n = S.g1, &g2n = S.g2;
             int ix = lane < RSN ? lane : -1;       // one slot: the compact row is the dense row
             int ixh = -1;
             if constexpr (row_slots<ND>() == 2) {
@@ -3259,8 +3315,10 @@ HD void substep(SimCtx& c, float hdt) {
                 ix = compact_index(lane, D, so0, so1);
                 if (VW == 2) ixh = compact_index(lane + 64, D, so0, so1);
             }
-            j0n = 0.f; j1n = 0.f; j2n = 0.f; y0n = 0.f; y1n = 0.f; y2n = 0.f;
-            h0n = 0.f; h1n = 0.f; h2n = 0.f; g0n = 0.f; g1n = 0.f; g2n = 0.f;
+            if constexpr (!NZF) {
+                j0n = 0.f; j1n = 0.f; j2n = 0.f; y0n = 0.f; y1n = 0.f; y2n = 0.f;
+                h0n = 0.f; h1n = 0.f; h2n = 0.f; g0n = 0.f; g1n = 0.f; g2n = 0.f;
+            }
             if constexpr (PC::rc) {
                 // object coordinates recomputed from the contact entry (obj_entry: the rows phase's values);
                 // robot coordinates from the contact's link slot (LDS for the first KL, else the spill rows)
@@ -3312,19 +3370,72 @@ HD void substep(SimCtx& c, float hdt) {
                 int lsc = (CAP * NCH <= 64 || ci < 64) ? bcast_i(lsl0, ci) : bcast_i(lsl1, ci - 64);
 #endif
                 bool lds_obj = LCH == NCH || ci < CAP * LCH;
+                if constexpr (UF) {
+                    // object lanes: the object block of contact ci, in LDS or (chunks LCH..) in the global row area;
+                    // robot lanes: the robot block of slot lsc, in LDS (< KL), in the global spill rows, or none.
+                    // Every condition but the lane's kind is wave-uniform, and so are the block offsets (scalar
+                    // arithmetic; -DHA_X_PGS_FETCH_MUL, A/B: a per-lane product)
+                    const bool rob_l = lsc >= 0 && lsc < KL, rob_g = lsc >= KL;
+                    if (lsc < 0 && f_rb) { j0n = 0.f; j1n = 0.f; j2n = 0.f; y0n = 0.f; y1n = 0.f; y2n = 0.f; }
+                    // the lane's block offset: br, or bo in the object lanes (their mask selects the difference)
+                    if (lds_obj || rob_l) {
+                        if (f_ob ? lds_obj : (f_rb && rob_l)) {
+#ifdef HA_X_PGS_FETCH_MUL
+                            const uint32_t o = f_lo + 3u * f_st * (uint32_t)(f_ob ? ci : lsc);
+#else
+                            const uint32_t bo = 12u * OW * ci, br = 12u * ND * lsc;
+                            const uint32_t o = f_lo + br + (f_obm & (bo - br));
+#endif
+                            const HA_AS_LDS char* P = (const HA_AS_LDS char*)Ob;
+                            const uint32_t o1 = o + f_st, o2 = o1 + f_st;
+                            j0n = *(const HA_AS_LDS float*)(P + o);
+                            j1n = *(const HA_AS_LDS float*)(P + o1);
+                            j2n = *(const HA_AS_LDS float*)(P + o2);
+                            y0n = *(const HA_AS_LDS float*)(P + (o + f_ly));
+                            y1n = *(const HA_AS_LDS float*)(P + (o1 + f_ly));
+                            y2n = *(const HA_AS_LDS float*)(P + (o2 + f_ly));
+                        }
+                    }
+                    if (!lds_obj || rob_g) {
+                        if (f_ob ? !lds_obj : (f_rb && rob_g)) {
+#ifdef HA_X_PGS_FETCH_MUL
+                            const uint32_t o = f_go + 3u * f_st * (uint32_t)(f_ob ? ci : lsc - KL);
+#else
+                            const uint32_t bo = 12u * OW * ci, br = 12u * ND * (lsc - KL);
+                            const uint32_t o = f_go + br + (f_obm & (bo - br));
+#endif
+                            const HA_AS_GLB char* G = (const HA_AS_GLB char*)c.spill;
+                            const uint32_t o1 = o + f_st, o2 = o1 + f_st;
+                            j0n = *(const HA_AS_GLB float*)(G + o);
+                            j1n = *(const HA_AS_GLB float*)(G + o1);
+                            j2n = *(const HA_AS_GLB float*)(G + o2);
+                            y0n = *(const HA_AS_GLB float*)(G + (o + f_gy));
+                            y1n = *(const HA_AS_GLB float*)(G + (o1 + f_gy));
+                            y2n = *(const HA_AS_GLB float*)(G + (o2 + f_gy));
+                        }
+                    }
+                    return;
+                }
 #ifndef HA_X_PGS_FETCH_GENERIC
                 if (lds_obj && lsc < KL) {
                     // every entry of this contact is in LDS: one set of six LDS loads from one base (the rows' J), each
                     // lane's block (object block of contact ci at stride OW, or robot block of slot lsc at stride ND)
-                    // chosen by offsets. With one object slot ix is the lane's own, so everything here but the
-                    // (ci | lsc) multiple is invariant over the contacts and the sweeps
+                    // chosen by offsets. The block's offset (3 OW ci | 3 ND lsc) is wave-uniform, scalar arithmetic;
+                    // a lane takes one of the two and adds its own offset within the block, which with one object slot
+                    // (ix is the lane's own) is invariant over the contacts and the sweeps.
+                    // (-DHA_X_PGS_FETCH_MUL, A/B: the block's offset as a per-lane product)
                     constexpr int oOY = RPC * LCH * OW, oR = 2 * oOY, oRY = oR + 3 * KL * ND;   // ObY, Rb, RbY from Ob
                     bool ob = ix >= D, rb = ix >= 0 && ix < D && lsc >= 0;
                     int o0 = ob ? ix - D : oR + ix;
                     int st = ob ? OW : ND;
                     int dy = ob ? oOY : oRY - oR;
                     if (ob || rb) {
+#ifdef HA_X_PGS_FETCH_MUL
                         const HA_AS_LDS float* P = (const HA_AS_LDS float*)Ob + (o0 + 3 * st * (ob ? ci : lsc));
+#else
+                        const int bo = 3 * OW * ci, br = 3 * ND * lsc;      // wave-uniform
+                        const HA_AS_LDS float* P = (const HA_AS_LDS float*)Ob + (o0 + (ob ? bo : br));
+#endif
                         j0n = P[0]; j1n = P[st]; j2n = P[2 * st];
                         y0n = P[dy]; y1n = P[dy + st]; y2n = P[dy + 2 * st];
                     }
@@ -3386,10 +3497,6 @@ HD void substep(SimCtx& c, float hdt) {
             if (PC::ovf && ci >= CAP) ldd(glb_f<TF>(gJ + 3 * (ci - CAP) * RSN), glb_f<TF>(gY + 3 * (ci - CAP) * RSN));   // wave-uniform
             else ldd(lds_f<TF>(J + 3 * ci * RSN), lds_f<TF>(Y + 3 * ci * RSN));
         };
-        auto advance = [&]() {
-            j0n = j0m; j1n = j1m; j2n = j2m; y0n = y0m; y1n = y1m; y2n = y2m;
-            h0n = h0m; h1n = h1m; h2n = h2m; g0n = g0m; g1n = g1m; g2n = g2m;
-        };
         // packed families: a contact block's constants (impulses, target velocities, 1/diagonals of its three rows, the
         // friction coefficient, the Delassus entries a10 a20 a21) - from RK (LDS), or with overflow chunks from the
         // registers of the lanes that own its rows in chunk 0 - and the serial block's arithmetic on them (n0, d0,
@@ -3428,8 +3535,12 @@ HD void substep(SimCtx& c, float hdt) {
                 int ci = lk0 ? __ffsll((unsigned long long)lk0) - 1 : 64 + __ffsll((unsigned long long)lk1) - 1;
                 if (ci < 64) lk0 &= lk0 - 1ull;
                 else lk1 &= lk1 - 1ull;
-                fetch(ci);
-                advance();
+                // no look-ahead here: straight into the set the block reads (zero-filled: a packed family's compact
+                // index changes with the contact)
+                RowSet S;
+                fetch(ci, S);
+                const float j0n = S.j0, j1n = S.j1, j2n = S.j2, y0n = S.y0, y1n = S.y1, y2n = S.y2;
+                const float h0n = S.h0, h1n = S.h1, h2n = S.h2, g0n = S.g0, g1n = S.g1, g2n = S.g2;
                 float jv0 = j0n * vreg, jv1 = j1n * vreg, jv2 = j2n * vreg;
                 if (VW == 2) {
                     jv0 = jv0 + h0n * vregh;
@@ -3508,8 +3619,49 @@ HD void substep(SimCtx& c, float hdt) {
                 wsync();
             }
         } else {
-        if (nc > 0) { fetch(0); advance(); }
-        if (nc > 1) fetch(1);
+        // one contact block: the rows of contact ci (chunk ch) from the set S
+        auto solve = [&](int ci, int ch, const RowSet& S) {
+            int r0 = 3 * (ci - CAP * ch);       // row of this contact within the chunk (= its lane)
+            float jv0 = S.j0 * vreg, jv1 = S.j1 * vreg, jv2 = S.j2 * vreg;
+            if (VW == 2) {
+                jv0 = jv0 + S.h0 * vregh;
+                jv1 = jv1 + S.h1 * vregh;
+                jv2 = jv2 + S.h2 * vregh;
+            }
+            wave_sum_rows3(jv0, jv1, jv2);
+            // the block's three rows live in lanes r0, r0 + 1, r0 + 2: each lane evaluates its own row with
+            // its own lambda and constants (the oracle's operands) and only n0, d0, d1, d2 cross lanes
+            float lm = klam;
+            float n0 = lm - (jv0 - kvt) * kwinv;
+            n0 = n0 < 0.0f ? 0.0f : (n0 > 3.0e38f ? 3.0e38f : n0);
+            float d0 = bcast(n0 - lm, r0);
+            n0 = bcast(n0, r0);
+            float hi = kcmu * n0;
+            float n1 = lm - (fmaf(kca0, d0, jv1) - kvt) * kwinv;
+            n1 = n1 < -hi ? -hi : (n1 > hi ? hi : n1);
+            float d1 = bcast(n1 - lm, r0 + 1);
+            float n2 = lm - (fmaf(kca1, d1, fmaf(kca0, d0, jv2)) - kvt) * kwinv;
+            n2 = n2 < -hi ? -hi : (n2 > hi ? hi : n2);
+            float d2 = bcast(n2 - lm, r0 + 2);
+            if (lane == r0) klam = n0;
+            if (lane == r0 + 1) klam = n1;
+            if (lane == r0 + 2) klam = n2;
+            if (d0 != 0.0f) { vreg = fmaf(S.y0, d0, vreg); if (VW == 2) vregh = fmaf(S.g0, d0, vregh); }
+            if (d1 != 0.0f) { vreg = fmaf(S.y1, d1, vreg); if (VW == 2) vregh = fmaf(S.g1, d1, vregh); }
+            if (d2 != 0.0f) { vreg = fmaf(S.y2, d2, vreg); if (VW == 2) vregh = fmaf(S.g2, d2, vregh); }
+            // the velocity update ends here (an empty statement that pins it): moved down to the next block's products
+            // it would read S after the fetch that refills S, and S would be copied (and waited for) first
+            if constexpr (ROT) asm volatile("" : "+v"(vreg));
+        };
+        // set A holds the rows of the contact that starts a trip, B the next one's, C the one after that
+        RowSet A, B, C;
+        if constexpr (ROT) {
+            if (nc > 0) fetch(0, A);
+            if (nc > 1) fetch(1, B);
+        } else {
+            if (nc > 0) { fetch(0, C); B = C; }
+            if (nc > 1) fetch(1, C);
+        }
 #pragma unroll 1
         for (int ch = 0; ch < NCH; ch++) {
             int cend = nc < CAP * (ch + 1) ? nc : CAP * (ch + 1);
@@ -3524,39 +3676,30 @@ HD void substep(SimCtx& c, float hdt) {
                     if (nca > 1 && lane < RPC) stage(nx);
                 }
             }
-            for (int ci = CAP * ch; ci < cend; ci++) {
-                int r0 = 3 * (ci - CAP * ch);       // row of this contact within the chunk (= its lane)
-                float j0 = j0n, j1 = j1n, j2 = j2n, y0 = y0n, y1 = y1n, y2 = y2n;
-                float h0 = h0n, h1 = h1n, h2 = h2n, g0 = g0n, g1 = g1n, g2 = g2n;
-                advance();
-                if (ci + 2 < nc) fetch(ci + 2);
-                float jv0 = j0 * vreg, jv1 = j1 * vreg, jv2 = j2 * vreg;
-                if (VW == 2) {
-                    jv0 = jv0 + h0 * vregh;
-                    jv1 = jv1 + h1 * vregh;
-                    jv2 = jv2 + h2 * vregh;
+            if constexpr (ROT) {
+                // a trip is three contacts; CAP is a multiple of three, so every chunk starts a trip with set A and
+                // only the list's last chunk can end on a part of one (cend == nc there: nothing is left to prefetch)
+                int ci = CAP * ch;
+#pragma unroll 1
+                for (; ci + 3 <= cend; ci += 3) {
+                    if (ci + 2 < nc) fetch(ci + 2, C);
+                    solve(ci, ch, A);
+                    if (ci + 3 < nc) fetch(ci + 3, A);
+                    solve(ci + 1, ch, B);
+                    if (ci + 4 < nc) fetch(ci + 4, B);
+                    solve(ci + 2, ch, C);
                 }
-                wave_sum_rows3(jv0, jv1, jv2);
-                // the block's three rows live in lanes r0, r0 + 1, r0 + 2: each lane evaluates its own row with
-                // its own lambda and constants (the oracle's operands) and only n0, d0, d1, d2 cross lanes
-                float lm = klam;
-                float n0 = lm - (jv0 - kvt) * kwinv;
-                n0 = n0 < 0.0f ? 0.0f : (n0 > 3.0e38f ? 3.0e38f : n0);
-                float d0 = bcast(n0 - lm, r0);
-                n0 = bcast(n0, r0);
-                float hi = kcmu * n0;
-                float n1 = lm - (fmaf(kca0, d0, jv1) - kvt) * kwinv;
-                n1 = n1 < -hi ? -hi : (n1 > hi ? hi : n1);
-                float d1 = bcast(n1 - lm, r0 + 1);
-                float n2 = lm - (fmaf(kca1, d1, fmaf(kca0, d0, jv2)) - kvt) * kwinv;
-                n2 = n2 < -hi ? -hi : (n2 > hi ? hi : n2);
-                float d2 = bcast(n2 - lm, r0 + 2);
-                if (lane == r0) klam = n0;
-                if (lane == r0 + 1) klam = n1;
-                if (lane == r0 + 2) klam = n2;
-                if (d0 != 0.0f) { vreg = fmaf(y0, d0, vreg); if (VW == 2) vregh = fmaf(g0, d0, vregh); }
-                if (d1 != 0.0f) { vreg = fmaf(y1, d1, vreg); if (VW == 2) vregh = fmaf(g1, d1, vregh); }
-                if (d2 != 0.0f) { vreg = fmaf(y2, d2, vreg); if (VW == 2) vregh = fmaf(g2, d2, vregh); }
+                if (ci < cend) {
+                    solve(ci, ch, A);
+                    if (ci + 1 < cend) solve(ci + 1, ch, B);
+                }
+            } else {
+                for (int ci = CAP * ch; ci < cend; ci++) {
+                    RowSet S = B;
+                    B = C;
+                    if (ci + 2 < nc) fetch(ci + 2, C);
+                    solve(ci, ch, S);
+                }
             }
             if (multi && lane < RPC) rk(0, RPC * ch + lane) = klam;     // swap the impulses out
         }

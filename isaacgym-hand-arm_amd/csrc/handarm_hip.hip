@@ -361,7 +361,7 @@ __device__ void snapshot_from_tensors(SimCtx& c, const ha_state_t& st, int env, 
 
 // always inlined: as an outlined call (the inliner's choice once it grows past its threshold) the step runs
 // ~40% slower (call ABI: stack spills, no cross-phase register allocation)
-template <class PC>
+template <class PC, bool SETS3 = true>
 // n_calls gym.simulate calls. An applied object force (ha_state_t.object_force for ha_simulate, the tasks' random
 // forces) lasts one call: apply_rigid_body_force_tensors acts on the next simulate (the oracle's simulate_env alike)
 __device__ __forceinline__ void run_physics(SimCtx& c, int n_calls) {
@@ -369,7 +369,7 @@ __device__ __forceinline__ void run_physics(SimCtx& c, int n_calls) {
     for (int k = 0; k < n_calls; k++) {
         for (int sub = 0; sub < c.p->substeps; sub++) {
             c.last = k == n_calls - 1 && sub == c.p->substeps - 1;
-            substep<PC>(c, hdt);
+            substep<PC, SETS3>(c, hdt);
         }
         if (c.lane < c.NO) {
             c.o[c.lane].ofx[0] = c.o[c.lane].ofx[1] = c.o[c.lane].ofx[2] = 0.0f;
@@ -617,7 +617,9 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
     }
     load_env(c, S, env, MODE == MODE_SIMULATE);
     if (MODE == MODE_SIMULATE) {
-        run_physics<PC>(c, n_calls);
+        // ak_simulate_kernel keeps the PGS copy loop: the three row sets cost it 16 B/lane of scratch (20 -> 36; the
+        // fused step kernel, which the tasks run, stays at 28 with them)
+        run_physics<PC, TASK != HA_TASK_ALLEGRO_KUKA>(c, n_calls);
         after_physics(c, env);
         store_env(c, S, env);
         return;
