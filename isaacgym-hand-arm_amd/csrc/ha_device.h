@@ -80,15 +80,11 @@ HD int lane_id() { return threadIdx.x & 63; }
 // wavefront-scope release / acquire pair is then all the ordering needed: it stops the compiler from moving
 // memory operations across the point, and unlike __syncthreads() (workgroup scope: s_waitcnt lgkmcnt(0) at every
 // call even with the s_barrier elided for one wave) it does not stall on in-flight LDS and scalar loads.
-#ifdef HA_X_WSYNC_BLOCK     /* A/B: the workgroup-scope barrier */
-HD void wsync() { __syncthreads(); }
-#else
 HD void wsync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-#endif
 
 // value of lane `src` in every lane; src must be wave-uniform (v_readlane_b32 -> SGPR)
 HD float bcast(float x, int src) {
@@ -121,14 +117,10 @@ HD float lane63(float x) { return __int_as_float(__builtin_amdgcn_readlane(__flo
 // one cross-row step of a sum whose only reader is lane 63: x + (x moved by CTRL in the rows of RM). The lanes outside
 // the row mask get an undefined addend, so the step is two instructions (a defined `old` costs a third, the v_mov that
 // sets it). Lane 63 never sees an undefined lane: its row is enabled in both steps, and the lane 31 it takes in the
-// second step was enabled in the first. -DHA_X_ROWSUM_ZERO_OLD (A/B): old = 0, the three-instruction step
+// second step was enabled in the first (against old = 0: profiles/r08_pgs_sweep.txt)
 template <int CTRL, int RM>
 HD float dpp_row_add(float x) {
-#ifdef HA_X_ROWSUM_ZERO_OLD
-    return x + dpp_row_f<CTRL, RM>(0.0f, x);
-#else
     return x + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(x), CTRL, RM, 0xF, false));
-#endif
 }
 
 // sum of the four row results: (r3 + r2) + (r1 + r0) in lane 63

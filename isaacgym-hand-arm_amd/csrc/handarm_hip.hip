@@ -1259,10 +1259,8 @@ extern "C" __global__ void __launch_bounds__(1024) ha_env_order_kernel(const int
         for (int q = t; q < n; q += 1024) {
             unsigned long long d = t1[q] >= t0[q] ? t1[q] - t0[q] : 0ull;
             int v = d > 0x7FFFFFFFull ? 0x7FFFFFFF : (int)d;
-#ifndef HA_X_ORDER_LAST_SPAN    /* A/B: the last span alone */
             // half the last span plus half the previous estimate (C5 +1%, C4 +0.7% against the last span alone)
             v = (int)(((long long)v + cost_prev[order[q]]) >> 1);
-#endif
             cost_prev[order[q]] = v;
             m = v > m ? v : m;
         }
@@ -1274,9 +1272,6 @@ extern "C" __global__ void __launch_bounds__(1024) ha_env_order_kernel(const int
         // the span scaled so that the longest lands in bucket 0 (the spans of a long launch, C5's ~7 ms per env,
         // would saturate a fixed unit), or the contacts offered since the last refresh
         int cost = t1 ? (int)((long long)cost_prev[e] * 1023 / smax) : stats[HA_CSTAT * (size_t)e + 3] - cost_prev[e];
-#ifdef HA_X_ORDER_FIXED_UNIT    /* A/B: the fixed 5.12 us bucket of the first span-based order */
-        if (t1) cost = cost_prev[e] >> 9;
-#endif
         return 1023 - (cost < 0 ? 0 : (cost > 1023 ? 1023 : cost));      // bucket 0: the most expensive envs
     };
     cnt[t] = 0;
