@@ -29,6 +29,10 @@
  *                                  (vec_task.py:437, allegro_kuka_base.py:908-917)
  *   ha_task_step_io                VecTask.step whole for the Allegro tasks: the action clamp (vec_task.py:400-404),
  *                                  the fused step and the epilogue's outputs, in ONE launch
+ *   ha_bind_dr_replay              np.random.uniform / np.random.normal of generate_random_samples
+ *                                  (utils/dr_utils.py:98-130) and the noise lambdas' torch.randn_like / rand_like
+ *                                  (vec_task.py:700-754): their draws, made on the host and replayed by the kernels
+ *                                  (HA_FLAG_REPLAY_DR)
  *   ha_pointclouds                 synthetic point-cloud observables' post_step refresh
  *                                  (multi_object.py:792-809, ur5sih.py:361-374)
  *   ha_gather_obs                  compute_observations' torch.cat for a custom observation list
@@ -188,6 +192,7 @@ typedef struct ha_dr_attr_t {
 #define HA_FLAG_NO_PHYSICS 1u      /* skip physics substeps (task-math parity tests) */
 #define HA_FLAG_REPLAY_DRAWS 2u    /* reset draws come from ha_state_t.reset_draws (host RNG replay) */
 #define HA_FLAG_OBS_ONLY 4u        /* ha_task_observe: compute_observations only (VecTask.reset) */
+#define HA_FLAG_REPLAY_DR 8u       /* DR draws come from the buffers bound with ha_bind_dr_replay (host RNG replay) */
 
 /* Static scene model (built offline by tools/build_model.py, packed by handarm_hip/model.py). */
 typedef struct ha_model_t {
@@ -556,6 +561,27 @@ typedef struct ha_camera_t {
     uint32_t rng_counter;       /* per-call counter of the random subset when more than P points are on the target */
 } ha_camera_t;
 
+/* Additive v16 extension (no struct above changes, HA_ABI_VERSION stays 16): replayed domain-randomization draws.
+ * With HA_FLAG_REPLAY_DR on a step / step_io / reset / observe launch, every DR sample comes from these caller-owned
+ * device buffers instead of the counter hash, so a host that draws like the reference (handarm_hip/ref_rng.py DrDraws)
+ * gets the reference's randomness:
+ *   dr_draws, dr_gravity_draws   np.random.uniform / np.random.normal of generate_random_samples
+ *                                (utils/dr_utils.py:98-130, called from apply_randomizations,
+ *                                tasks/base/vec_task.py:756-864): the quantile in [0, 1) of a uniform / loguniform
+ *                                sample, the standard normal of a gaussian one
+ *   dr_*_corr, dr_*_white        torch.randn_like / torch.rand_like of the noise lambdas (vec_task.py:700-754): corr is
+ *                                always a standard normal, white a standard normal (gaussian) or U[0, 1) (uniform)
+ * The device still decides which envs sample and whether the non-env randomization runs (HA_DRG_*); a slot is read only
+ * when its sample is made. A buffer whose quantities the schema leaves off may be null. */
+typedef struct ha_dr_replay_t {
+    const float* dr_draws;          /* [N][HA_DR_SIZE]: slot s = the draw of the sample that fills dr_scale slot s */
+    const float* dr_gravity_draws;  /* [3] */
+    const float* dr_obs_corr;       /* [N][num_obs] */
+    const float* dr_obs_white;      /* [N][num_obs] */
+    const float* dr_act_corr;       /* [N][num_actions] */
+    const float* dr_act_white;      /* [N][num_actions] */
+} ha_dr_replay_t;
+
 typedef struct ha_handle_s* ha_handle;
 
 int ha_abi_version(void);
@@ -566,6 +592,10 @@ int ha_struct_sizes(int32_t* model_size, int32_t* params_size, int32_t* state_si
 int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_envs, ha_handle* out);
 int ha_destroy(ha_handle h);
 int ha_bind_state(ha_handle h, const ha_state_t* state);
+/* v16 extension: bind (or, with NULL, unbind) the replayed DR draws, while no launch of the handle is in flight; the
+ * pointers are copied and must stay valid while launches carry HA_FLAG_REPLAY_DR. HA_E_ARG when a buffer the handle's
+ * schema samples from is null. A launch with HA_FLAG_REPLAY_DR and nothing bound returns HA_E_STATE. */
+int ha_bind_dr_replay(ha_handle h, const ha_dr_replay_t* replay);
 /* gym-style tensor API */
 int ha_simulate(ha_handle h, int32_t n_calls, uint32_t flags, void* stream);
 /* v9: ha_simulate for a subset of envs (device array of n_envs distinct env indices; the other envs do not move).

@@ -246,7 +246,8 @@ HD void ah_post(SimCtx& c, const ha_state_t& st, int env, const AhIn& in, bool o
             // compute_full_observations(no_vel=True) (:439-446): dof pos, object pose, goal pose, qdiff, actions
             v = full_state(k < 16 ? k : (k < 23 ? k + 32 : k + 38));
         }
-        if (!obs_only) v = dr_obs(c, env, k, v);        // DR observation noise on obs_buf (vec_task.py:426-428)
+        // DR observation noise on obs_buf (vec_task.py:426-428)
+        if (!obs_only) v = dr_obs(c, env, k, v, (size_t)env * nobs + k);
         ob[k] = v;
         obs_out_put(c, (size_t)env * nobs + k, v);
     }

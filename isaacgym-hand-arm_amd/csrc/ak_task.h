@@ -438,7 +438,8 @@ HD void ak_post(SimCtx& c, const ha_state_t& st, int env, AkPost& ak, bool obs_o
     for (int k = lane; k < nobs; k += 64) {
         float v = ak.obs[k];
         if (clampv > 0.0f && !obs_only) v = fminf(fmaxf(v, -clampv), clampv);   // clamp_obs (post_physics_step)
-        if (!obs_only) v = dr_obs(c, env, k, v);        // DR observation noise on obs_buf (vec_task.py:426-428)
+        // DR observation noise on obs_buf (vec_task.py:426-428)
+        if (!obs_only) v = dr_obs(c, env, k, v, (size_t)env * nobs + k);
         og[k] = v;
         obs_out_put(c, (size_t)env * nobs + k, v);
     }

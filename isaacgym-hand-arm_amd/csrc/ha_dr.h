@@ -14,6 +14,10 @@
 //     and writes an observation, white and correlated terms from the counter hash (no noise tensors in HBM).
 // Every sample is a function of (seed, env, counter, index) through uniform01 / dr_gauss, whose log / sine come from
 // include/ha_fmath.h, so oracle/dr_oracle.py restates the rows, the global state and the noise bit for bit.
+// Under HA_FLAG_REPLAY_DR (sim.reference_rng) the draw itself comes from the host instead: the reference's
+// np.random.uniform / np.random.normal quantiles and normals (dr_utils.py:98-130) and its randn_like / rand_like noise
+// tensors (vec_task.py:700-754), uploaded into the buffers of ha_bind_dr_replay (SimCtx.rp) and read with plain
+// per-lane loads of consecutive floats; the gates, schedules and arithmetic stay the ones above and below.
 #pragma once
 #include "ha_physics.h"
 
@@ -112,24 +116,32 @@ HD float dr_value(const ha_dr_attr_t& a, double r0, double r1, float og, float u
     return (float)v;
 }
 
-// one randomized quantity of this env, element k (lane-parallel callers): the dr_scale entry it leaves
-HD float dr_attr_sample(const ha_params_t& p, int attr, int env, uint32_t ep, int k, int frame, float og) {
+// one randomized quantity of this env, element k (lane-parallel callers): the dr_scale entry it leaves. rd: the env's
+// row of replayed draws (ha_dr_replay_t.dr_draws under HA_FLAG_REPLAY_DR; null: the counter hash), whose slot `slot`
+// (the dr_scale slot being filled) holds the host's quantile / standard normal for this sample
+HD float dr_attr_sample(const ha_params_t& p, int attr, int env, uint32_t ep, int k, int frame, float og,
+                        const float* rd, int slot) {
     const ha_dr_attr_t& a = p.dr_attr[attr];
     double r0, r1;
     dr_range(a, frame, r0, r1);
-    uint32_t key = 64u * (uint32_t)attr + (uint32_t)k;
     float u = 0.0f, g = 0.0f;
-    if (a.dist == HA_DR_DIST_GAUSSIAN) g = dr_gauss(p.seed ^ DR_SALT_ENV, env, ep, key);
-    else u = uniform01(p.seed ^ DR_SALT_ENV, env, ep, key);
+    if (rd) {
+        u = g = rd[slot];
+    } else {
+        uint32_t key = 64u * (uint32_t)attr + (uint32_t)k;
+        if (a.dist == HA_DR_DIST_GAUSSIAN) g = dr_gauss(p.seed ^ DR_SALT_ENV, env, ep, key);
+        else u = uniform01(p.seed ^ DR_SALT_ENV, env, ep, key);
+    }
     return dr_value(a, r0, r1, og, u, g);
 }
 // mass attributes keep the ratio new / nominal mass (inertia scales with it: recomputeInertia, dr_utils.py:63-64);
 // og: the value the reference's sample multiplies (its original_props entry), own: the body's nominal mass
-HD float dr_mass_ratio(const ha_params_t& p, int attr, int env, uint32_t ep, int k, int frame, float og, float own) {
+HD float dr_mass_ratio(const ha_params_t& p, int attr, int env, uint32_t ep, int k, int frame, float og, float own,
+                       const float* rd, int slot) {
     const ha_dr_attr_t& a = p.dr_attr[attr];
     if (a.op == HA_DR_OP_SCALING && a.num_buckets == 0 && og == own)
-        return dr_attr_sample(p, attr, env, ep, k, frame, 1.0f);
-    return dr_attr_sample(p, attr, env, ep, k, frame, og) / own;
+        return dr_attr_sample(p, attr, env, ep, k, frame, 1.0f, rd, slot);
+    return dr_attr_sample(p, attr, env, ep, k, frame, og, rd, slot) / own;
 }
 HD bool dr_active(const ha_params_t& p, int attr, bool all) {
     const ha_dr_attr_t& a = p.dr_attr[attr];
@@ -174,37 +186,47 @@ HD void dr_env_pre(SimCtx& c, const ha_state_t& st, int env, bool full, bool ste
     if (st.randomize_buf && lane == 0) st.randomize_buf[env] = rb + (step ? 1 : 0);
     if (!smp) return;
     float* row = st.dr_scale + (size_t)env * HA_DR_SIZE;
+    // replayed draws (HA_FLAG_REPLAY_DR): the env's row, same slots as `row`; a lane reads the slot it fills
+    const float* rd = c.rp ? c.rp->dr_draws + (size_t)env * HA_DR_SIZE : nullptr;
     uint32_t ep = st.episode[env];
     if (lane < c.L) {
         // after the first randomization the robot's list properties may take the object's original value (later_og)
         if (dr_elem(p, HA_DRA_LINK_MASS, all, lane)) {
             float own = m.link_mass[lane];
             float og = (!all && p.dr_attr[HA_DRA_LINK_MASS].later_og_object) ? m.pool_mass[c.o[0].pool] : own;
-            row[HA_DR_LINK_MASS + lane] = dr_mass_ratio(p, HA_DRA_LINK_MASS, env, ep, lane, frame, og, own);
+            row[HA_DR_LINK_MASS + lane] = dr_mass_ratio(p, HA_DRA_LINK_MASS, env, ep, lane, frame, og, own, rd,
+                                                          HA_DR_LINK_MASS + lane);
         }
         if (dr_elem(p, HA_DRA_LINK_FRIC, all, lane))
-            row[HA_DR_LINK_FRIC + lane] = dr_attr_sample(p, HA_DRA_LINK_FRIC, env, ep, lane, frame, p.friction);
+            row[HA_DR_LINK_FRIC + lane] = dr_attr_sample(p, HA_DRA_LINK_FRIC, env, ep, lane, frame, p.friction, rd,
+                                                           HA_DR_LINK_FRIC + lane);
     }
     if (lane < c.D) {
         if (dr_active(p, HA_DRA_DOF_KD, all))
-            row[HA_DR_DOF_KD + lane] = dr_attr_sample(p, HA_DRA_DOF_KD, env, ep, lane, frame, m.dof_kd[lane]);
+            row[HA_DR_DOF_KD + lane] = dr_attr_sample(p, HA_DRA_DOF_KD, env, ep, lane, frame, m.dof_kd[lane], rd,
+                                                      HA_DR_DOF_KD + lane);
         if (dr_active(p, HA_DRA_DOF_KP, all))
-            row[HA_DR_DOF_KP + lane] = dr_attr_sample(p, HA_DRA_DOF_KP, env, ep, lane, frame, m.dof_kp[lane]);
+            row[HA_DR_DOF_KP + lane] = dr_attr_sample(p, HA_DRA_DOF_KP, env, ep, lane, frame, m.dof_kp[lane], rd,
+                                                      HA_DR_DOF_KP + lane);
         if (dr_active(p, HA_DRA_DOF_LOWER, all))
-            row[HA_DR_DOF_LOWER + lane] = dr_attr_sample(p, HA_DRA_DOF_LOWER, env, ep, lane, frame, m.dof_lower[lane]);
+            row[HA_DR_DOF_LOWER + lane] = dr_attr_sample(p, HA_DRA_DOF_LOWER, env, ep, lane, frame, m.dof_lower[lane],
+                                                         rd, HA_DR_DOF_LOWER + lane);
         if (dr_active(p, HA_DRA_DOF_UPPER, all))
-            row[HA_DR_DOF_UPPER + lane] = dr_attr_sample(p, HA_DRA_DOF_UPPER, env, ep, lane, frame, m.dof_upper[lane]);
+            row[HA_DR_DOF_UPPER + lane] = dr_attr_sample(p, HA_DRA_DOF_UPPER, env, ep, lane, frame, m.dof_upper[lane],
+                                                         rd, HA_DR_DOF_UPPER + lane);
     }
     bool rescale = dr_active(p, HA_DRA_OBJ_SCALE, all);
     if (lane < c.NO) {
         int o = lane;
         if (dr_active(p, HA_DRA_OBJ_MASS, all))
             row[HA_DR_OBJ_MASS + o] = dr_mass_ratio(p, HA_DRA_OBJ_MASS, env, ep, o, frame, m.pool_mass[c.o[o].pool],
-                                                    m.pool_mass[c.o[o].pool]);
+                                                    m.pool_mass[c.o[o].pool], rd, HA_DR_OBJ_MASS + o);
         if (dr_active(p, HA_DRA_OBJ_FRIC, all))
-            row[HA_DR_OBJ_FRIC + o] = dr_attr_sample(p, HA_DRA_OBJ_FRIC, env, ep, o, frame, p.friction);
+            row[HA_DR_OBJ_FRIC + o] = dr_attr_sample(p, HA_DRA_OBJ_FRIC, env, ep, o, frame, p.friction, rd,
+                                                     HA_DR_OBJ_FRIC + o);
         if (rescale) {
-            row[HA_DR_OBJ_SCALE + o] = dr_attr_sample(p, HA_DRA_OBJ_SCALE, env, ep, o, frame, 1.0f);
+            row[HA_DR_OBJ_SCALE + o] = dr_attr_sample(p, HA_DRA_OBJ_SCALE, env, ep, o, frame, 1.0f, rd,
+                                                      HA_DR_OBJ_SCALE + o);
             dr_object_scale(c, st, env, o);
             // the COM offset moves with the scale: the object's pose (origin) stays where the root state put it
             const float* r = st.root_state + ((size_t)env * m.n_actors + m.actor_object0 + o) * 13;
@@ -223,19 +245,28 @@ HD void dr_env_pre(SimCtx& c, const ha_state_t& st, int env, bool full, bool ste
 // noise of one element (vec_task.py:718-726 gaussian, 745-752 uniform): op(x, (corr * P0 + P1) + white * P2 + P3) with
 // corr ~ N(0, 1) per (env, element) redrawn at each non-env randomization (the reference's randn_like even for the
 // uniform distribution) and white ~ N(0, 1) (gaussian) or U[0, 1) (uniform) per step
+// rc / rw: the replayed corr / white tensors (HA_FLAG_REPLAY_DR; rc null: the counter hash), element i = (env, k)
 HD float dr_noise(const ha_dr_attr_t& a, const float* P, uint64_t sw, uint64_t sc, int env, uint32_t step,
-                  uint32_t epoch, int k, float x) {
-    float corr = dr_gauss(sc, env, epoch, k);
-    float white = a.dist == HA_DR_DIST_GAUSSIAN ? dr_gauss(sw, env, step, k) : uniform01(sw, env, step, k);
+                  uint32_t epoch, int k, float x, const float* rc, const float* rw, size_t i) {
+    float corr, white;
+    if (rc) {
+        corr = rc[i];
+        white = rw[i];
+    } else {
+        corr = dr_gauss(sc, env, epoch, k);
+        white = a.dist == HA_DR_DIST_GAUSSIAN ? dr_gauss(sw, env, step, k) : uniform01(sw, env, step, k);
+    }
     float n = ((corr * P[0] + P[1]) + white * P[2]) + P[3];
     return a.op == HA_DR_OP_SCALING ? x * n : x + n;
 }
-// obs_buf element k of this env after post_physics_step (vec_task.py:426-428)
-HD float dr_obs(const SimCtx& c, int env, int k, float x) {
+// obs_buf element k of this env after post_physics_step (vec_task.py:426-428); i: its index in the obs tensor, which
+// is also its index in the replayed noise tensors
+HD float dr_obs(const SimCtx& c, int env, int k, float x, size_t i) {
     const float* G = c.drg;
     if (!G || !drg_i(G, HA_DRG_VALID) || c.p->dr_attr[HA_DRA_OBS].dist == HA_DR_DIST_OFF) return x;
     return dr_noise(c.p->dr_attr[HA_DRA_OBS], G + HA_DRG_OBS, c.p->seed ^ DR_SALT_OBS_W, c.p->seed ^ DR_SALT_OBS_C, env,
-                    (uint32_t)drg_i(G, HA_DRG_STEP), (uint32_t)drg_i(G, HA_DRG_EPOCH), k, x);
+                    (uint32_t)drg_i(G, HA_DRG_STEP), (uint32_t)drg_i(G, HA_DRG_EPOCH), k, x,
+                    c.rp ? c.rp->dr_obs_corr : nullptr, c.rp ? c.rp->dr_obs_white : nullptr, i);
 }
 
 // action k of this env as the task reads it: the caller's raw action (ha_task_step_io) or the bound actions tensor,
@@ -247,7 +278,8 @@ HD float act_at(const SimCtx& c, const ha_state_t& st, int env, int k, int na) {
     const float* G = c.drg;
     if (G && drg_i(G, HA_DRG_ACT_ON))
         a = dr_noise(c.p->dr_attr[HA_DRA_ACT], G + HA_DRG_ACT_USE, c.p->seed ^ DR_SALT_ACT_W, c.p->seed ^ DR_SALT_ACT_C,
-                     env, (uint32_t)drg_i(G, HA_DRG_STEP), (uint32_t)drg_i(G, HA_DRG_ACT_EPOCH), k, a);
+                     env, (uint32_t)drg_i(G, HA_DRG_STEP), (uint32_t)drg_i(G, HA_DRG_ACT_EPOCH), k, a,
+                     c.rp ? c.rp->dr_act_corr : nullptr, c.rp ? c.rp->dr_act_white : nullptr, i);
     if (c.act_in) a = fminf(fmaxf(a, -c.clip_act), c.clip_act);
     return a;
 }
@@ -274,7 +306,8 @@ HD void dr_noise_params(const ha_dr_attr_t& a, int frame, float* P) {
 // The shard-wide part of apply_randomizations before a step (mode 0) or reset (mode 1) launch; `any`: some env's
 // reset_buf is set (reset_idx, and with it apply_randomizations, runs). Frames: the gym.simulate calls of the launch
 // (control_freq_inv, plus the Ur5Sih reset_idx's extra call when an env resets).
-HD void dr_global_update(const ha_params_t& p, float* g, int any, int mode) {
+// rg: the replayed gravity draws (ha_dr_replay_t.dr_gravity_draws under HA_FLAG_REPLAY_DR; null: the counter hash).
+HD void dr_global_update(const ha_params_t& p, float* g, int any, int mode, const float* rg) {
     auto gi = [&](int k) -> int { return __float_as_int(g[k]); };
     auto si = [&](int k, int v) { g[k] = __int_as_float(v); };
     if (mode == 0) {
@@ -313,7 +346,8 @@ HD void dr_global_update(const ha_params_t& p, float* g, int any, int mode) {
             dr_range(a, frame, r0, r1);
             for (int k = 0; k < 3; k++) {
                 float u = 0.0f, gg = 0.0f;
-                if (a.dist == HA_DR_DIST_GAUSSIAN) gg = dr_gauss(p.seed ^ DR_SALT_GRAV, 0, (uint32_t)epoch, k);
+                if (rg) u = gg = rg[k];
+                else if (a.dist == HA_DR_DIST_GAUSSIAN) gg = dr_gauss(p.seed ^ DR_SALT_GRAV, 0, (uint32_t)epoch, k);
                 else u = uniform01(p.seed ^ DR_SALT_GRAV, 0, (uint32_t)epoch, k);
                 float og = all ? p.gravity[k] : g[HA_DRG_GRAVITY_OG + k];
                 float v = dr_value(a, r0, r1, og, u, gg);

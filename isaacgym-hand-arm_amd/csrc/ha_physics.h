@@ -374,6 +374,8 @@ struct SimCtx {
     int maxc;               // contact capacity (MAXC x chunks of the kernel family)
     const float* dr;        // this env's domain-randomization row (HA_DR_*), or null when DR is off
     const float* drg;       // v16: the shard-wide randomization state (ha_state_t.dr_global, HA_DRG_*), null: DR off
+    const ha_dr_replay_t* rp;   // HA_FLAG_REPLAY_DR: the replay buffers (device copy of ha_bind_dr_replay's struct);
+                                // null: every DR draw from the counter hash
     float* spill;           // split rows: this env's global robot-block rows beyond the LDS slots (J, then Y)
     // narrow-phase cache: (hull, body) whose world vertices / planes are in ColScratch side A / side B. Within one
     // detect() the poses do not change, so consecutive pairs that share a side skip its setup (same values).

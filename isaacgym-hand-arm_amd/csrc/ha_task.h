@@ -241,7 +241,7 @@ HD void post_step(SimCtx& c, const ha_state_t& st, int env, const ObsIn& in, boo
     for (int e = lane; e < NOBS; e += 64) {
         float v = ob[e];
         st.teacher_obs[(size_t)env * NOBS + e] = v;
-        if (!obs_only) v = dr_obs(c, env, e, v);
+        if (!obs_only) v = dr_obs(c, env, e, v, (size_t)env * NOBS + e);
         st.obs[(size_t)env * NOBS + e] = v;
     }
     if (obs_only) return;     // VecTask.reset(): compute_observations without a refresh

@@ -465,6 +465,9 @@ struct StepIO {
     // dispatch-order refresh (null: off)
     unsigned long long* tstart;
     unsigned long long* tend;
+    // HA_FLAG_REPLAY_DR (every mode): the device copy of the bound ha_dr_replay_t; null without the flag, so no launch
+    // without it reads the replay buffers
+    const ha_dr_replay_t* drr;
 };
 
 // AllegroKuka extras: mean prev_episode_successes, mean / min / max true_objective over the shard, in the step launch.
@@ -588,6 +591,7 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
     // v16: the shard-wide DR state (ha_dr_global_kernel ran before this launch); with it the per-env sampling, the
     // noise and the randomized gravity are on
     c.drg = (c.dr && st.dr_global) ? st.dr_global : nullptr;
+    c.rp = io.drr;
     ObsIn& in = c.s->u.pd.in;
     AhIn& ain = *reinterpret_cast<AhIn*>(&c.s->u.pd.in);
     AkPost& akp = *reinterpret_cast<AkPost*>(&c.s->u.pd.in);
@@ -812,7 +816,8 @@ extern "C" __global__ void ha_copy_indexed_kernel(float* dst, const float* src, 
 // lane updates dr_global. force_any: the launch resets every env regardless of the flags (the Ur5Sih reset launch).
 extern "C" __global__ void __launch_bounds__(256) ha_dr_global_kernel(const ha_params_t* __restrict__ params,
                                                                        const int64_t* __restrict__ reset_buf, int n,
-                                                                       float* __restrict__ g, int mode, int force_any) {
+                                                                       float* __restrict__ g, int mode, int force_any,
+                                                                       const float* __restrict__ grav_draws) {
     __shared__ int any;
     if (threadIdx.x == 0) any = force_any;
     __syncthreads();
@@ -820,7 +825,7 @@ extern "C" __global__ void __launch_bounds__(256) ha_dr_global_kernel(const ha_p
     for (int i = threadIdx.x; i < n; i += 256) a |= reset_buf[i] != 0 ? 1 : 0;
     if (a) any = 1;                     // every writer stores 1
     __syncthreads();
-    if (threadIdx.x == 0) dr_global_update(*params, g, any, mode);
+    if (threadIdx.x == 0) dr_global_update(*params, g, any, mode, grav_draws);
 }
 
 // ----------------------------------------------------------------------------- step epilogue
@@ -906,6 +911,9 @@ struct ha_handle_s {
     unsigned long long* d_tend;
     float* d_io_partials; // AllegroKuka extras: 4 floats per group of 64 envs
     int32_t* d_io_counters;   // and ceil(N / 64) + 1 counters, zero between launches
+    ha_dr_replay_t h_drr;     // ha_bind_dr_replay: the caller's buffers (host copy; drr_bound 0: none)
+    ha_dr_replay_t* d_drr;    // and the device copy the kernels read under HA_FLAG_REPLAY_DR
+    int drr_bound;
 };
 
 #define HIPCHK(x)                                                                     \
@@ -1190,6 +1198,7 @@ int ha_destroy(ha_handle h) {
     if (h->d_io_counters) (void)hipFree(h->d_io_counters);
     if (h->d_tstart) (void)hipFree(h->d_tstart);
     if (h->d_tend) (void)hipFree(h->d_tend);
+    if (h->d_drr) (void)hipFree(h->d_drr);
     (void)hipEventDestroy(h->ev0);
     (void)hipEventDestroy(h->ev1);
     free(h);
@@ -1207,9 +1216,35 @@ int ha_bind_state(ha_handle h, const ha_state_t* state) {
     return HA_OK;
 }
 
+// v16 extension: the replayed DR draws (include/handarm_abi.h ha_dr_replay_t). Every buffer the handle's schema
+// samples from must be there, so a launch under HA_FLAG_REPLAY_DR never reads a null pointer.
+int ha_bind_dr_replay(ha_handle h, const ha_dr_replay_t* replay) {
+    if (!h) return HA_E_ARG;
+    if (!replay) {
+        h->drr_bound = 0;
+        return HA_OK;
+    }
+    const ha_params_t& p = h->h_params;
+    auto on = [&](int k) { return p.dr_attr[k].dist != HA_DR_DIST_OFF; };
+    bool actor = false;
+    for (int k = HA_DRA_LINK_MASS; k < HA_DRA_N; k++) actor = actor || on(k);
+    if (actor && !replay->dr_draws) return HA_E_ARG;
+    if (on(HA_DRA_GRAVITY) && !replay->dr_gravity_draws) return HA_E_ARG;
+    if (on(HA_DRA_OBS) && !(replay->dr_obs_corr && replay->dr_obs_white)) return HA_E_ARG;
+    if (on(HA_DRA_ACT) && !(replay->dr_act_corr && replay->dr_act_white)) return HA_E_ARG;
+    if (!h->d_drr) HIPCHK(hipMalloc(&h->d_drr, sizeof(ha_dr_replay_t)));
+    HIPCHK(hipMemcpy(h->d_drr, replay, sizeof(ha_dr_replay_t), hipMemcpyHostToDevice));
+    h->h_drr = *replay;
+    h->drr_bound = 1;
+    return HA_OK;
+}
+
 static int launch(ha_handle h, int mode, int n_calls, uint32_t flags, int slot, void* stream,
                   const int32_t* env_ids = nullptr, int n_ids = 0) {
     if (!h || !h->bound) return HA_E_STATE;
+    if ((flags & HA_FLAG_REPLAY_DR) && !h->drr_bound) return HA_E_STATE;
+    StepIO io = mode == MODE_STEP ? h->io : StepIO{};
+    io.drr = (flags & HA_FLAG_REPLAY_DR) ? h->d_drr : nullptr;
     hipStream_t s = (hipStream_t)stream;
     // HIP events only while timing is enabled (ha_enable_kernel_timing): an event record in the stream costs a few
     // microseconds of GPU idle between the kernels, which a training loop should not pay
@@ -1220,8 +1255,7 @@ static int launch(ha_handle h, int mode, int n_calls, uint32_t flags, int slot, 
         n_ids = h->N;
     }
     hipLaunchKernelGGL(kernel_for(h->fam, mode), dim3(env_ids ? n_ids : h->N), dim3(64), lds_bytes(h->fam), s, h->d_model,
-                       h->d_params, h->st, h->N, n_calls, flags, slot, h->d_spill, env_ids,
-                       mode == MODE_STEP ? h->io : StepIO{});
+                       h->d_params, h->st, h->N, n_calls, flags, slot, h->d_spill, env_ids, io);
     HIPCHK(hipGetLastError());
     if (rec) {
         (void)hipEventRecord(h->t_ev[2 * h->t_count + 1], s);
@@ -1446,10 +1480,11 @@ static bool task_bound(ha_handle h) {
 }
 
 // the shard-wide DR update before a step / reset launch (dr_enable only)
-static int dr_global(ha_handle h, int mode, void* stream) {
+static int dr_global(ha_handle h, int mode, uint32_t flags, void* stream) {
     if (!h->h_params.dr_enable) return HA_OK;
     hipLaunchKernelGGL(ha_dr_global_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, h->d_params, h->st.reset_buf,
-                       h->N, h->st.dr_global, mode, mode == 1 && h->task == HA_TASK_UR5SIH ? 1 : 0);
+                       h->N, h->st.dr_global, mode, mode == 1 && h->task == HA_TASK_UR5SIH ? 1 : 0,
+                       (flags & HA_FLAG_REPLAY_DR) ? h->h_drr.dr_gravity_draws : nullptr);
     HIPCHK(hipGetLastError());
     return HA_OK;
 }
@@ -1458,10 +1493,11 @@ int ha_task_step(ha_handle h, uint32_t flags, void* stream) {
     if (!h || !h->bound || !h->st.actions || !h->st.obs || !h->st.stats || !h->st.term_sums || !task_bound(h))
         return HA_E_STATE;
     if (h->stat_slots < 2) return HA_E_STATE;
+    if ((flags & HA_FLAG_REPLAY_DR) && !h->drr_bound) return HA_E_STATE;     // before the stats ring moves on
     int slot = (int)(h->step_counter % h->stat_slots);
     int next = (int)((h->step_counter + 1) % h->stat_slots);
     h->step_counter++;
-    int rc = dr_global(h, 0, stream);
+    int rc = dr_global(h, 0, flags, stream);
     if (rc != HA_OK) return rc;
     rc = launch(h, MODE_STEP, next, flags, slot, stream);         // clears `next` for the following step
     if (rc == HA_OK && h->task == HA_TASK_ALLEGRO_HAND && h->st.consecutive_successes) {
@@ -1503,6 +1539,7 @@ int ha_task_epilogue(ha_handle h, float* obs_out, float clip_obs, float* scalars
 
 int ha_task_observe(ha_handle h, uint32_t flags, void* stream) {
     if (!h || !h->bound || !h->st.obs || !task_bound(h)) return HA_E_STATE;
+    if ((flags & HA_FLAG_REPLAY_DR) && !h->drr_bound) return HA_E_STATE;
     HIPCHK(hipMemsetAsync(h->st.stats, 0, sizeof(int32_t) * HA_STAT_SIZE, (hipStream_t)stream));
     HIPCHK(hipMemsetAsync(h->st.term_sums, 0, sizeof(float) * 4, (hipStream_t)stream));
     return launch(h, MODE_OBSERVE, 0, flags, 0, stream);
@@ -1510,7 +1547,8 @@ int ha_task_observe(ha_handle h, uint32_t flags, void* stream) {
 
 int ha_task_reset(ha_handle h, uint32_t flags, void* stream) {
     if (!h || !h->bound || !task_bound(h)) return HA_E_STATE;
-    int rc = dr_global(h, 1, stream);
+    if ((flags & HA_FLAG_REPLAY_DR) && !h->drr_bound) return HA_E_STATE;
+    int rc = dr_global(h, 1, flags, stream);
     if (rc != HA_OK) return rc;
     return launch(h, MODE_RESET, 0, flags, 0, stream);
 }

@@ -24,6 +24,7 @@ SIGNATURES = {
     "ha_create": ([C.POINTER(HM.HaModel), C.POINTER(HM.HaParams), C.c_int32, C.POINTER(H)], C.c_int),
     "ha_destroy": ([H], C.c_int),
     "ha_bind_state": ([H, C.POINTER(HM.HaState)], C.c_int),
+    "ha_bind_dr_replay": ([H, C.POINTER(HM.HaDrReplay)], C.c_int),
     "ha_simulate": ([H, C.c_int32, C.c_uint32, S], C.c_int),
     "ha_simulate_envs": ([H, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, S], C.c_int),
     "ha_refresh": ([H, S], C.c_int),

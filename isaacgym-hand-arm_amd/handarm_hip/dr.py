@@ -26,8 +26,12 @@ What is built, per key of the schema (anything else raises NotImplementedError):
   reset_idx after the sim is initialised (vec_task.py:286-289, allegro_kuka_base.py:1248), so its setup_only
   attributes are never applied, as there.
 
-The samples come from the device counter hash, not numpy's global generator: the distributions and schedules are the
-reference's, the draws are not seed-faithful (parity: tests/test_dr_schema.py, tests/test_gpu_dr_schema.py).
+By default the samples come from the device counter hash, not numpy's global generator: the distributions and
+schedules are the reference's, the draws are not seed-faithful (parity: tests/test_dr_schema.py,
+tests/test_gpu_dr_schema.py). With ``sim.reference_rng`` the AllegroKuka / AllegroHand classes draw them on the host
+from numpy's and torch's global generators in the reference's order and the kernels replay them (HA_FLAG_REPLAY_DR,
+handarm_hip/ref_rng.py DrDraws). For that the host has to know how many draws a launch will consume: ``gate`` below
+restates the device's decision (it does not make it), and ``draw_plan`` keeps the schema's property order.
 """
 import copy
 
@@ -171,8 +175,26 @@ def _attr(spec, where, noise=False, setup_only=False):
     return a
 
 
+# property group of the schema -> the draw plan's group name
+GROUPS = {"dof_properties": "dof", "rigid_body_properties": "body", "rigid_shape_properties": "shape"}
+
+
 def parse(rp, task):
     """randomization_params -> (frequency, {HA_DRA_*: HaDrAttr}). NotImplementedError for any key not built."""
+    return _parse(rp, task)[:2]
+
+
+def draw_plan(rp, task):
+    """The actor properties in the order apply_randomizations walks them (vec_task.py:788-864: actors, then each
+    actor's properties, then a property's attributes, all in the schema's dict order): a list of
+    (actor kind "robot" / "object", group "dof" / "body" / "shape" / "scale", [HA_DRA_* in attribute order]), with the
+    attributes the parse dropped (AllegroKuka's setup_only ones) left out. ref_rng.DrDraws draws in this order."""
+    _, attrs, plan = _parse(rp, task)
+    plan = [(kind, group, [k for k in idxs if k in attrs]) for kind, group, idxs in plan]
+    return [e for e in plan if e[2]]
+
+
+def _parse(rp, task):
     if rp is None:
         rp = DEFAULT_SCHEMA[task]
     rp = copy.deepcopy(dict(rp))
@@ -192,6 +214,7 @@ def parse(rp, task):
         attrs[HM.DRA_GRAVITY] = _attr(spec, "sim_params.gravity")
     actors = ACTORS[task]
     order = []                                   # (actor kind, property) in the schema's order
+    plan = []                                    # draw_plan entries, in the schema's order
     for actor, props in (rp.pop("actor_params", None) or {}).items():
         if actor not in actors:
             raise NotImplementedError(f"randomization_params actor_params.{actor}: the {sorted(actors)} actors are "
@@ -206,10 +229,12 @@ def parse(rp, task):
                     raise NotImplementedError(f"randomization_params {where}: only the object actor's scale is "
                                               f"implemented")
                 attrs[HM.DRA_OBJ_SCALE] = _attr(pattrs, where)
+                plan.append((kind, "scale", [HM.DRA_OBJ_SCALE]))
                 continue
             if not isinstance(pattrs, dict) or not any(k[:2] == (kind, prop) for k in PROPS):
                 raise NotImplementedError(f"randomization_params {where} is not implemented")
             order.append((kind, prop))
+            plan.append((kind, GROUPS[prop], [PROPS.get((kind, prop, attr)) for attr in pattrs]))
             # one setup_only attribute keeps the whole property from being set again (vec_task.py:843-864)
             group_setup = any(isinstance(v, dict) and v.get("setup_only", False) for v in pattrs.values())
             for attr, spec in pattrs.items():
@@ -237,7 +262,7 @@ def parse(rp, task):
     if task == HM.TASK_ALLEGRO_KUKA:
         # the first apply_randomizations runs from reset_idx, after sim_initialized: setup_only never applies
         attrs = {k: a for k, a in attrs.items() if not a.setup_only}
-    return frequency, attrs
+    return frequency, attrs, plan
 
 
 def apply_schema(p, rp, task):
@@ -275,6 +300,25 @@ def init_global(params):
     g[HM.DRG_GRAVITY:HM.DRG_GRAVITY + 3] = list(params.gravity)
     g[HM.DRG_GRAVITY_OG:HM.DRG_GRAVITY_OG + 3] = list(params.gravity)
     return g
+
+
+def gate(g, frequency, reset, randomize_buf):
+    """What the next step / reset launch will decide (csrc/ha_dr.h dr_global_update, dr_env_pre), restated on the host
+    from the state the launch will read: g = dr_global before the launch (HA_DRG_*, int fields as int32 bits), reset =
+    the reset flags, randomize_buf = the per-env counts. Returns (nonenv, all, envs): the non-env randomization runs,
+    it is the first randomization (every env samples), and the bool mask of the envs that sample. The device keeps
+    deciding; the host only needs the count of draws to make (ref_rng.DrDraws.apply)."""
+    gi = np.ascontiguousarray(np.asarray(g, np.float32)).view(np.int32)
+    reset = np.asarray(reset) != 0
+    rb = np.asarray(randomize_buf)
+    nonenv = all_ = False
+    if reset.any():                       # reset_idx, and with it apply_randomizations, runs when an env resets
+        if gi[HM.DRG_FIRST]:
+            nonenv = all_ = True
+        else:
+            nonenv = bool(int(gi[HM.DRG_FRAME_NEXT]) - int(gi[HM.DRG_LAST_RAND]) >= frequency)
+    envs = np.ones(len(reset), bool) if all_ else (reset & (rb >= frequency))
+    return nonenv, all_, envs
 
 
 def describe(params):

@@ -56,6 +56,7 @@ AK_REWARD_KEYS = ["raw_fingertip_delta_rew", "raw_hand_delta_penalty", "raw_lift
 FLAG_NO_PHYSICS = 1
 FLAG_REPLAY_DRAWS = 2
 FLAG_OBS_ONLY = 4
+FLAG_REPLAY_DR = 8        # DR draws from the buffers of ha_bind_dr_replay (handarm_hip/ref_rng.py DrDraws)
 NP_NO_EDGE_AXES, NP_NO_CLIP = 1, 2      # ha_params_t.narrow_phase_flags
 
 f32, i32 = C.c_float, C.c_int32
@@ -238,6 +239,14 @@ def state_spec(num_envs, n_links=29, n_dofs=17, n_obj=3, num_initial_poses=1, nu
 
 class HaState(C.Structure):
     _fields_ = [(n, P) for n in STATE_FIELDS]
+
+
+DR_REPLAY_FIELDS = ["dr_draws", "dr_gravity_draws", "dr_obs_corr", "dr_obs_white", "dr_act_corr", "dr_act_white"]
+
+
+class HaDrReplay(C.Structure):
+    """ha_dr_replay_t (include/handarm_abi.h, v16 extension): the replayed DR draws (device pointers)."""
+    _fields_ = [(n, P) for n in DR_REPLAY_FIELDS]
 
 
 PC_MAX_LINKS = 32

@@ -12,6 +12,18 @@ the reference's reset indexing (target object, object configuration, goal, cube/
 The price is one device->host read of the reset flags per step (the reference reads them too, with
 ``nonzero()``) and one small upload.
 
+Domain randomization (``task.randomize``) follows the same switch for AllegroKuka and AllegroHand: ``DrDraws`` makes
+the reference's numpy draws of apply_randomizations (utils/dr_utils.py:98-130 through tasks/base/vec_task.py:756-864)
+and the torch draws of its two noise lambdas (vec_task.py:700-754) on the host, in the reference's order, and the
+kernels replay them (HA_FLAG_REPLAY_DR, the buffers of ha_bind_dr_replay). The device still decides which envs sample
+(csrc/ha_dr.h); the host restates that decision (handarm_hip/dr.py gate) to know how many draws to make, which adds
+one more small device->host read per step (randomize_buf and the 32-float dr_global, one copy) and a few uploads: the
+white noise tensors every step, the correlated ones and the sampled envs' draw rows when they are redrawn. Nobody
+has measured that cost; the default hash path pays none of it.
+Ur5Sih keeps today's behaviour with both switches on: its schema is the build's own (handarm_hip/dr.py
+UR5SIH_SCHEMA; the reference's Ur5Sih DR flag has no consumer), so there is no reference stream to follow and its
+DR samples stay on the device counter hash.
+
 Each function cites the reference lines whose draws it reproduces; the kernel-side slot layouts are documented
 in csrc/ha_task.h (Ur5Sih), csrc/ak_task.h (AllegroKuka) and csrc/ah_task.h (AllegroHand).
 """
@@ -175,6 +187,169 @@ class AllegroDraws:
             D[idx[:, 0], 47:50] = g[:, 0, :]
             D[idx[:, 0], 50] = 1.0                                      # the selection (ah_task.h AH_DRAW_FORCE_SEL)
         return D
+
+
+# --------------------------------------------------------------------------- domain randomization
+# HA_DRA_* of an actor property -> first dr_scale / dr_draws slot of its elements
+DR_SLOT = {HM.DRA_LINK_MASS: HM.DR_LINK_MASS, HM.DRA_LINK_FRIC: HM.DR_LINK_FRIC, HM.DRA_DOF_KD: HM.DR_DOF_KD,
+           HM.DRA_DOF_KP: HM.DR_DOF_KP, HM.DRA_DOF_LOWER: HM.DR_DOF_LOWER, HM.DRA_DOF_UPPER: HM.DR_DOF_UPPER,
+           HM.DRA_OBJ_MASS: HM.DR_OBJ_MASS, HM.DRA_OBJ_FRIC: HM.DR_OBJ_FRIC, HM.DRA_OBJ_SCALE: HM.DR_OBJ_SCALE}
+# the reference schemas' order (AllegroKuka.yaml:143-207, AllegroHand.yaml:88-150), when no plan is given
+DR_PLAN = [("robot", "dof", [HM.DRA_DOF_KD, HM.DRA_DOF_KP, HM.DRA_DOF_LOWER, HM.DRA_DOF_UPPER]),
+           ("robot", "body", [HM.DRA_LINK_MASS]), ("robot", "shape", [HM.DRA_LINK_FRIC]),
+           ("object", "scale", [HM.DRA_OBJ_SCALE]), ("object", "body", [HM.DRA_OBJ_MASS]),
+           ("object", "shape", [HM.DRA_OBJ_FRIC])]
+U_BELOW_ONE = np.float32(1.0 - 2.0 ** -24)      # a double quantile just under 1 must not round up to 1
+
+
+class DrApplied:
+    """One apply_randomizations call's draws: `nonenv` / `all` / `envs` as dr.gate returns them, `draws` the
+    (N, HA_DR_SIZE) float32 rows (the sampled envs' drawn slots filled, zero elsewhere), `gravity` the 3 gravity draws
+    (None when this call drew none)."""
+
+    def __init__(self, nonenv, all_, envs, draws, gravity):
+        self.nonenv, self.all, self.envs, self.draws, self.gravity = nonenv, all_, envs, draws, gravity
+
+
+class DrDraws:
+    """The reference's DR draws of one VecTask.step on the host's global generators, in its order.
+
+    ``apply`` is one apply_randomizations call (vec_task.py:646-876): numpy's legacy global stream, through
+    ``np.random.uniform(0, 1, shape)`` / ``np.random.normal(0, 1, shape)``, which consume it exactly as the
+    reference's ``uniform(lo, hi, shape)`` / ``normal(mu, var, shape)`` (dr_utils.py:98-130) do; the quantile / standard
+    normal is what the kernel takes (csrc/ha_dr.h dr_value scales it with the scheduled range). Order: the sim_params
+    gravity 3-vector when the non-env part runs (:756-786), then per actor in the schema's order, per sampled env in
+    ascending id, per property in the schema's order (:788-864): a dof_properties attribute is one D-vector, a body /
+    shape list property goes element by element and attribute by attribute within it, the object's scale is one draw;
+    after the first randomization a robot list property draws only its ``later_elems`` elements and setup_only
+    attributes draw nothing (handarm_hip/dr.py).
+
+    ``noise`` is the torch side of one VecTask.step (vec_task.py:390-441) on the global CPU generator: the action
+    lambda, the task's own pre-physics draws (KukaDraws.step / AllegroDraws.step), the observation lambda. A lambda
+    draws ``corr`` (randn of the tensor's shape) when a non-env randomization has run since it last did, then
+    ``white`` (randn, or rand for the uniform distribution); VecTask.reset() adds no noise and draws nothing.
+
+    params / model: the sim's HaParams / HaModel; plan: dr.draw_plan of the schema (None: the reference yamls' order).
+    """
+
+    def __init__(self, params, model, num_envs, plan=None):
+        self.n = int(num_envs)
+        self.frequency = int(params.dr_frequency)
+        a = params.dr_attr
+        self.dist = [int(a[k].dist) for k in range(HM.DRA_N)]
+        self.setup_only = [int(a[k].setup_only) for k in range(HM.DRA_N)]
+        self.later_elems = [int(a[k].later_elems) for k in range(HM.DRA_N)]
+        self.L, self.D, self.NO = int(model.n_links), int(model.n_dofs), int(params.n_objects)
+        if self.NO != 1:
+            raise NotImplementedError("reference_rng with task.randomize: one object actor (the Allegro scenes)")
+        self.num_obs, self.num_actions = int(params.num_obs), int(params.num_actions)
+        plan = DR_PLAN if plan is None else plan
+        self.actors = []                                  # [(kind, [(group, [HA_DRA_*])])] in the schema's order
+        for kind, group, idxs in plan:
+            idxs = [k for k in idxs if self.dist[k]]
+            if not idxs:
+                continue
+            if not self.actors or self.actors[-1][0] != kind:
+                self.actors.append((kind, []))
+            self.actors[-1][1].append((group, idxs))
+        # dr_randomizations of the two lambdas: filled by the first non-env randomization; its 'corr' entry is dropped
+        # by every later one (vec_task.py:727-728,753-754 replace the dict)
+        self.valid = False
+        self.pending = {HM.DRA_OBS: False, HM.DRA_ACT: False}
+
+    def _draw(self, k, shape):
+        """One generate_random_samples call of attribute k: float32 quantile(s) in [0, 1) or standard normal(s)."""
+        if self.dist[k] == HM.DR_DIST["gaussian"]:
+            return np.asarray(np.random.normal(0.0, 1.0, shape), np.float64).astype(np.float32)
+        u = np.asarray(np.random.uniform(0.0, 1.0, shape), np.float64).astype(np.float32)
+        return np.minimum(u, U_BELOW_ONE)
+
+    def _active(self, k, all_):
+        return self.dist[k] != 0 and (all_ or not self.setup_only[k])
+
+    def _elems(self, k, all_):
+        if not self._active(k, all_):
+            return 0
+        return self.L if (all_ or self.later_elems[k] < 0) else min(self.L, self.later_elems[k])
+
+    def apply(self, g, reset, randomize_buf):
+        """The draws of the apply_randomizations call the next step / reset launch will run. g: dr_global as that
+        launch will read it; reset: the reset flags; randomize_buf: the per-env counts (dr.gate). -> DrApplied."""
+        from . import dr as DR
+        nonenv, all_, envs = DR.gate(g, self.frequency, reset, randomize_buf)
+        gravity = None
+        if nonenv and self.dist[HM.DRA_GRAVITY]:
+            gravity = self._draw(HM.DRA_GRAVITY, 3)
+        rows = np.zeros((len(envs), HM.DR_SIZE), np.float32)
+        ids = np.nonzero(envs)[0]
+        for kind, groups in self.actors:
+            for e in ids:
+                row = rows[e]
+                for group, idxs in groups:
+                    if group == "dof":
+                        for k in idxs:
+                            if self._active(k, all_):
+                                row[DR_SLOT[k]:DR_SLOT[k] + self.D] = self._draw(k, self.D)
+                    elif kind == "robot":
+                        n = [self._elems(k, all_) for k in idxs]
+                        for i in range(max(n)):
+                            for k, nk in zip(idxs, n):
+                                if i < nk:
+                                    row[DR_SLOT[k] + i] = self._draw(k, 1)[0]
+                    else:
+                        for k in idxs:
+                            if self._active(k, all_):
+                                row[DR_SLOT[k]] = self._draw(k, 1)[0]
+        return DrApplied(nonenv, all_, envs, rows, gravity)
+
+    def _lambda(self, k, width):
+        """noise_lambda of observations / actions: (corr or None when it is not redrawn, white), CPU float32."""
+        if not self.valid or not self.dist[k]:
+            return None, None
+        corr = None
+        if self.pending[k]:
+            corr = torch.randn((self.n, width), dtype=torch.float32, device="cpu")
+            self.pending[k] = False
+        draw = torch.randn if self.dist[k] == HM.DR_DIST["gaussian"] else torch.rand
+        return corr, draw((self.n, width), dtype=torch.float32, device="cpu")
+
+    def noise(self, nonenv, task_draws=None, step=True):
+        """The torch draws of one VecTask.step. nonenv: this step's apply() ran the non-env randomization (the
+        observation lambda then redraws corr in this very step, the action lambda in the next); task_draws: a
+        callable making the task's own pre-physics draws between the two lambdas; step=False: a bare reset_idx call
+        (no lambda runs, the randomization is only noted). Returns {"act_corr", "act_white", "task", "obs_corr",
+        "obs_white"}: tensors to upload, None for what was not drawn."""
+        out = dict.fromkeys(("act_corr", "act_white", "task", "obs_corr", "obs_white"))
+        if step:
+            out["act_corr"], out["act_white"] = self._lambda(HM.DRA_ACT, self.num_actions)
+        if task_draws is not None:
+            out["task"] = task_draws()
+        if nonenv:
+            self.valid = True
+            self.pending[HM.DRA_OBS] = self.pending[HM.DRA_ACT] = True
+        if step:
+            out["obs_corr"], out["obs_white"] = self._lambda(HM.DRA_OBS, self.num_obs)
+        return out
+
+
+def dr_draws_for(sim, task):
+    """DrDraws of a HandArmSim with its replay buffers bound (the task classes, reference_rng + task.randomize)."""
+    from . import dr as DR
+    dd = DrDraws(sim.params, sim.model, sim.num_envs, DR.draw_plan(sim.cfg.get("randomization_params"), task))
+    sim.bind_dr_replay()
+    return dd
+
+
+def dr_replay_step(sim, dd, reset, task_draws, step=True):
+    """One step's (step=False: one bare reset_idx call's) DR draws for the launch that follows: the gate's inputs in
+    one device->host read (randomize_buf and dr_global; `reset` is the host copy of the reset flags the caller
+    already has), DrDraws.apply / noise around the task's own draws, and the uploads. Returns task_draws()'s result."""
+    n = sim.num_envs
+    buf = torch.cat([sim.t["randomize_buf"], sim.t["dr_global"].view(torch.int32)]).cpu().numpy()
+    res = dd.apply(buf[n:].view(np.float32), np.asarray(reset), buf[:n])
+    nz = dd.noise(res.nonenv, task_draws, step)
+    sim.upload_dr_replay(res, nz)
+    return nz["task"]
 
 
 _ = math

@@ -262,6 +262,39 @@ class HandArmSim:
         self._act_hold = a
         return a
 
+    def bind_dr_replay(self):
+        """Allocate and bind the replayed DR draws (ha_bind_dr_replay): launches with HM.FLAG_REPLAY_DR then take
+        every DR sample from ``self.dr_replay`` (name -> tensor, HM.DR_REPLAY_FIELDS) instead of the counter hash.
+        Launches without the flag do not read them. Idempotent."""
+        if getattr(self, "dr_replay", None) is not None:
+            return self.dr_replay
+        N, p = self.num_envs, self.params
+        shapes = {"dr_draws": (N, HM.DR_SIZE), "dr_gravity_draws": (3,), "dr_obs_corr": (N, p.num_obs),
+                  "dr_obs_white": (N, p.num_obs), "dr_act_corr": (N, p.num_actions),
+                  "dr_act_white": (N, p.num_actions)}
+        with torch.cuda.device(self.device):
+            bufs = {k: torch.zeros(shapes[k], dtype=torch.float32, device=self.device) for k in HM.DR_REPLAY_FIELDS}
+        self._dr_replay_struct = HM.HaDrReplay(**{k: v.data_ptr() for k, v in bufs.items()})
+        _lib.check(self.lib.ha_bind_dr_replay(self.h, C.byref(self._dr_replay_struct)), "ha_bind_dr_replay")
+        self.dr_replay = bufs
+        return bufs
+
+    def upload_dr_replay(self, applied=None, noise=None):
+        """Upload one step's host draws (handarm_hip/ref_rng.py DrDraws): `applied` (DrApplied: the sampled envs' draw
+        rows and the gravity draws, when it made any) and `noise` (DrDraws.noise: the tensors it redrew)."""
+        bufs = self.bind_dr_replay()
+        if applied is not None:
+            if applied.gravity is not None:
+                bufs["dr_gravity_draws"].copy_(torch.from_numpy(applied.gravity))
+            if applied.all:
+                bufs["dr_draws"].copy_(torch.from_numpy(applied.draws))
+            elif applied.envs.any():
+                ids = torch.from_numpy(applied.envs.nonzero()[0])
+                bufs["dr_draws"][ids.to(self.device)] = torch.from_numpy(applied.draws[applied.envs]).to(self.device)
+        for k, v in (noise or {}).items():
+            if k != "task" and v is not None:
+                bufs["dr_" + k].copy_(v)
+
     def task_observe(self, flags=0):
         _lib.check(self.lib.ha_task_observe(self.h, flags, self._stream()), "ha_task_observe")
 

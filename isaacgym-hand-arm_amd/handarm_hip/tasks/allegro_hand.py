@@ -110,6 +110,9 @@ class AllegroHand:
         self.reference_rng = bool(cfg.get("sim", {}).get("reference_rng", False))
         self._rr = RR.AllegroDraws(N, force_scale=self.sim.cfg["force_scale"],
                                    force_prob_range=self.sim.cfg["force_prob_range"]) if self.reference_rng else None
+        # with task.randomize as well, the DR draws follow: numpy's and torch's global generators in the reference's
+        # order, replayed by the kernels (ref_rng.DrDraws, HA_FLAG_REPLAY_DR)
+        self._dr = RR.dr_draws_for(self.sim, HM.TASK_ALLEGRO_HAND) if self.reference_rng and self.randomize else None
         self.extras = {}
         self.obs_dict = {}
         # obs_dict["obs"] = clamp(obs_buf) by the step launch (ha_task_step_io) into one of two alternating buffers: step t's obs
@@ -172,7 +175,8 @@ class AllegroHand:
         out = torch.empty_like(self._obs_out[0]) if self.fresh_outputs else self._obs_out[(self.control_steps + 1) & 1]
         # one launch: the action clamp into actions_buf (vec_task.py:400-404), the fused step and obs_dict["obs"] =
         # clamp(obs_buf) into `out` (ha_task_step_io)
-        self.sim.task_step_io(self.sim_flags | self._reference_draws(), actions, self.clip_actions, out, self.clip_obs)
+        self.sim.task_step_io(self.sim_flags | self._reference_draws(step=True), actions, self.clip_actions, out,
+                              self.clip_obs)
         self.control_steps += 1
         self.extras["time_outs"] = self.timeout_buf.view(torch.bool).to(self.rl_device)
         cs = self.consecutive_successes.view(())                                     # allegro_hand.py:393 (1 value)
@@ -203,14 +207,20 @@ class AllegroHand:
             self.reset_goal_buf[goal_env_ids] = 1
         self.sim.task_reset(self.sim_flags | self._reference_draws())
 
-    def _reference_draws(self):
+    def _reference_draws(self, step=False):
         """reference_rng: this step's reset draws on the host (one read of the reset flags), uploaded for
-        HA_FLAG_REPLAY_DRAWS. Returns the extra launch flags."""
+        HA_FLAG_REPLAY_DRAWS; with task.randomize also the DR draws around them (one more small read, uploaded for
+        HA_FLAG_REPLAY_DR; step: a VecTask.step, whose noise lambdas draw, not a bare reset_idx). Returns the extra
+        launch flags."""
         if self._rr is None:
             return 0
-        d = self._rr.step(self.reset_buf.cpu(), self.reset_goal_buf.cpu())
+        reset, goal = self.reset_buf.cpu(), self.reset_goal_buf.cpu()
+
+        def draws():
+            return self._rr.step(reset, goal)
+        d = draws() if self._dr is None else RR.dr_replay_step(self.sim, self._dr, reset.numpy(), draws, step=step)
         self.sim.t["reset_draws"].copy_(d)
-        return HM.FLAG_REPLAY_DRAWS
+        return HM.FLAG_REPLAY_DRAWS | (HM.FLAG_REPLAY_DR if self._dr is not None else 0)
 
     def reset_done(self):
         done_env_ids = self.reset_buf.nonzero(as_tuple=False).flatten()

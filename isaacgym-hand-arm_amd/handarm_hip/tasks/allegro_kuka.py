@@ -165,6 +165,9 @@ class AllegroKuka:
         if self.reference_rng:
             self._rr = RR.KukaDraws(N, sub, tuple(self.tcfg["force_prob_range"]), float(self.tcfg["force_scale"]))
             self.random_force_prob.copy_(self._rr.prob.to(sim_device))
+        # with task.randomize as well, the DR draws follow: numpy's and torch's global generators in the reference's
+        # order, replayed by the kernels (ref_rng.DrDraws, HA_FLAG_REPLAY_DR)
+        self._dr = RR.dr_draws_for(self.sim, HM.TASK_ALLEGRO_KUKA) if self.reference_rng and self.randomize else None
         # state dump / replay (allegro_kuka_base.py:95-101,545-546): off in AllegroKuka.yaml. Either one moves the
         # resets of a step into their own launch (ha_task_reset, then ha_task_step finds no reset flags), so the
         # loaded states can be written in between, as reset_idx does before its set_*_tensor_indexed calls
@@ -175,6 +178,9 @@ class AllegroKuka:
         self.initial_root_state_tensors = self.initial_dof_state_tensors = None
         self.initial_state_idx = self.num_initial_states = 0
         self._recorder = SF.EpisodeStateRecorder(N) if self.save_states else None
+        if self._dr is not None and (self.save_states or self.should_load_initial_states):
+            # the state files split a step's resets into their own launch, which would run the randomization gate twice
+            raise NotImplementedError("sim.reference_rng with task.randomize and saveStates / loadInitialStates")
         if self.should_load_initial_states:
             self.initial_root_state_tensors, self.initial_dof_state_tensors = SF.read_state_file(
                 self.load_states_filename, device=sim_device)
@@ -317,13 +323,21 @@ class AllegroKuka:
 
     def _reference_draws(self, forces=True):
         """reference_rng: this step's draws on the host (one read of the reset flags), uploaded for
-        HA_FLAG_REPLAY_DRAWS. Returns the extra launch flags."""
+        HA_FLAG_REPLAY_DRAWS; with task.randomize also the DR draws around them (one more small read, uploaded for
+        HA_FLAG_REPLAY_DR). Returns the extra launch flags."""
         if self._rr is None:
             return 0
         goal = self.reset_goal_buf.cpu() if forces else torch.zeros(self.num_envs, dtype=torch.int64)
-        d, _ = self._rr.step(self.reset_buf.cpu(), goal, forces=forces)
+        reset = self.reset_buf.cpu()
+
+        def draws():
+            return self._rr.step(reset, goal, forces=forces)
+        if self._dr is None:
+            d, _ = draws()
+        else:
+            d, _ = RR.dr_replay_step(self.sim, self._dr, reset.numpy(), draws, step=forces)
         self.sim.t["reset_draws"].copy_(d)
-        return HM.FLAG_REPLAY_DRAWS
+        return HM.FLAG_REPLAY_DRAWS | (HM.FLAG_REPLAY_DR if self._dr is not None else 0)
 
     def reset_done(self):
         done_env_ids = self.reset_buf.nonzero(as_tuple=False).flatten()
