@@ -91,6 +91,8 @@ HD float bcast(float x, int src) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), src));
 }
 HD int bcast_i(int x, int src) { return __builtin_amdgcn_readlane(x, src); }
+// whether the lane's bit is set in a wave-uniform mask: the mask itself becomes the condition (no per-lane shift)
+HD bool lane_in(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
 // value of lane `src` (per lane, 0..63; ds_bpermute_b32). A disabled source lane reads as 0: call it where the
 // source lanes are active
 HD int lane_read_i(int x, int src) { return __builtin_amdgcn_ds_bpermute(src << 2, x); }

@@ -621,6 +621,19 @@ HD void substep(SimCtx& c, float hdt) {
         lsl0 = lslot(lane);
         if (CAP * NCH > 64) lsl1 = lslot(lane + 64);
     }
+    // One row slot and split rows (UF below, AllegroKuka): lane i keeps the fetch descriptor of contact i (and of contact
+    // 64 + i) instead, one word built here, once per substep, of what a fetch would otherwise derive from the slot per
+    // contact and per sweep. Bits 0..13: the byte offset of the contact's object block (12 OW ci: within the LDS object
+    // blocks, or from chunk 0's place in the env's global row area when bit 14 is set). Bits 16..29: the byte offset of
+    // its robot block (12 ND slot within the LDS slots; 12 ND (slot - KL) within the global spill rows when bit 30 is
+    // set; 0 with bit 31 when the contact touches no link)
+    constexpr uint32_t FD_OG = 1u << 14, FD_RG = 1u << 30, FD_NL = 1u << 31, FD_GLB = FD_OG | FD_RG;
+    auto fdesc = [&](int ci) -> uint32_t {
+        int ls = lslot(ci);
+        uint32_t fo = 12u * OW * ci | (LCH == NCH || ci < CAP * LCH ? 0u : FD_OG);
+        uint32_t fr = ls < 0 ? FD_NL : (ls < KL ? 12u * ND * ls << 16 : (12u * ND * (ls - KL) << 16 | FD_RG));
+        return fo | fr;
+    };
     // several chunks: the row constants of the chunk after the current one, loaded while the current one is solved
     float sl = 0.f, svt = 0.f, swinv = 0.f, scmu = 0.f, sca0 = 0.f, sca1 = 0.f;
     auto stage = [&](int ch) {
@@ -655,22 +668,43 @@ HD void substep(SimCtx& c, float hdt) {
     // One row slot and split rows (AllegroKuka): a lane's compact index is its own for every contact, so everything
     // per lane in a fetch is fixed here, once per substep: whether it reads an object or a robot block, its offset
     // within the first such block in LDS (from Ob) and in the env's global area (from c.spill), the blocks' row stride
-    // and the distance from a J entry to its Y entry. A fetch adds the contact's wave-uniform block offset and issues
-    // one set of LDS loads and one of global loads, each under its own lane mask. The lanes that never have an entry
-    // keep the 0 their sets start each sweep with; only the robot lanes of a contact without a link are zeroed, for
-    // that contact alone. Dense rows with one row slot (AllegroHand) need no zero either: the same lanes load for every
-    // contact. The other families zero-fill the set before every fetch, as the copy loop does (it makes every lane
-    // wait for the set's previous loads)
+    // and the distance from a J entry to its Y entry. A fetch adds the block offset it cuts out of the contact's
+    // descriptor and issues one set of LDS loads in every lane (a lane without an entry reads the zero pad) and, for a
+    // contact with a block in the env's global area, one set of global loads in the lanes of that kind
+    // (profiles/r09_pgs_fetch.txt). Dense rows with one row slot (AllegroHand) need no zero either: the same lanes load
+    // for every contact. The other families zero-fill the set before every fetch, as the copy loop does (it makes
+    // every lane wait for the set's previous loads)
     constexpr bool UF = ROT && PC::split && !PC::rc && row_slots<ND>() == 1;
     constexpr bool NZF = UF || (ROT && !PC::split && row_slots<ND>() == 1);
     // (all in bytes, 32 bits: an LDS address is one, and a global load takes the scalar base with a 32-bit lane offset)
     constexpr int oOY = RPC * LCH * OW, oR = 2 * oOY, oRY = oR + 3 * KL * ND;   // ObY, Rb, RbY from Ob, in floats
     const bool f_ob = UF && lane >= D && lane < RSN, f_rb = UF && lane < D;
-    const uint32_t f_obm = f_ob ? ~0u : 0u;
+    // f_sh: where the lane's block offset starts in a contact's descriptor (a lane >= RSN has no block: its LDS loads
+    // read the zero pad whatever the field holds, and 0x4000 << 31 is no flag, so it never takes the global set)
+    const uint32_t f_sh = f_ob ? 0u : (f_rb ? 16u : 31u);
     const uint32_t f_st = 4u * (f_ob ? OW : ND);
-    const uint32_t f_lo = 4u * (f_ob ? lane - D : oR + lane), f_ly = 4u * (f_ob ? oOY : oRY - oR);
+    // LDS addresses (the address space's 32 bits), so that the pad, which lies in front of the rows, is one too
+    const uint32_t f_lb = (uint32_t)(uintptr_t)(const HA_AS_LDS float*)Ob;
+    const uint32_t f_lo = f_lb + 4u * (f_ob ? lane - D : oR + lane), f_ly = 4u * (f_ob ? oOY : oRY - oR);
     const uint32_t f_go = 4u * (f_ob ? PC::spill_robot - RPC * LCH * OW + (lane - D) : lane);
     const uint32_t f_gy = 4u * (f_ob ? RPC * (NCH - LCH) * OW : SPJ);
+    // The zero pad: the last word of the generalized velocity, which no coordinate of this family reaches. A lane
+    // without an entry reads it six times (both strides 0): the lanes >= RSN for every contact, the robot lanes for a
+    // contact that touches no link. So the LDS set of a fetch runs in every lane, under no lane mask
+    const uint32_t f_pad = (uint32_t)(uintptr_t)(const HA_AS_LDS float*)&s.v[MAXV - 1];
+    constexpr uint64_t FM_HI = RSN < 64 ? ~0ull << (RSN < 64 ? RSN : 0) : 0ull;                 // lanes >= RSN
+    constexpr uint64_t FM_NOB = FM_HI | ((1ull << (ND < 64 ? ND : 0)) - 1ull);                  // ... and the robot lanes
+    uint32_t fd0 = 0u, fd1 = 0u;
+    if constexpr (UF) {
+        static_assert(!UF || ND + 6 * PC::ocap < MAXV, "the zero pad is the velocity's last word");
+        static_assert(!UF || (12 * OW * CAP * NCH < (1 << 14) && 12 * ND * CAP * NCH < (1 << 14)), "descriptor fields");
+        static_assert(!UF || 12 * OW * CAP * NCH + 4 * (OW + oOY) <= (int)pc_rowdata_bytes<PC>(),
+                      "a global object block's offset, read as an LDS one, stays inside the rows");
+        fd0 = fdesc(lane);
+        if (CAP * NCH > 64) fd1 = fdesc(lane + 64);
+        if (lane == 0) *(HA_AS_LDS float*)&s.v[MAXV - 1] = 0.0f;
+        wsync();
+    }
 #ifdef HA_AB_PGS_TWICE
     for (int it = 0; it < 2 * p.solver_iters; it++) {
 #else
@@ -791,34 +825,36 @@ HD void substep(SimCtx& c, float hdt) {
                 // robot coordinates from the contact's link slot (LDS for the first KL, else the global spill rows),
                 // absent -> 0. LDS and global sources stay on separate paths (both conditions are wave-uniform)
                 // the contact's link slot from the lane that holds it (one v_readlane: ci is wave-uniform)
-                int lsc = (CAP * NCH <= 64 || ci < 64) ? bcast_i(lsl0, ci) : bcast_i(lsl1, ci - 64);
-                bool lds_obj = LCH == NCH || ci < CAP * LCH;
                 if constexpr (UF) {
                     // object lanes: the object block of contact ci, in LDS or (chunks LCH..) in the global row area;
-                    // robot lanes: the robot block of slot lsc, in LDS (< KL), in the global spill rows, or none.
-                    // Every condition but the lane's kind is wave-uniform, and so are the block offsets (scalar
-                    // arithmetic; against a per-lane product: profiles/r08_pgs_sweep.txt)
-                    const bool rob_l = lsc >= 0 && lsc < KL, rob_g = lsc >= KL;
-                    if (lsc < 0 && f_rb) { j0n = 0.f; j1n = 0.f; j2n = 0.f; y0n = 0.f; y1n = 0.f; y2n = 0.f; }
-                    // the lane's block offset: br, or bo in the object lanes (their mask selects the difference)
-                    if (lds_obj || rob_l) {
-                        if (f_ob ? lds_obj : (f_rb && rob_l)) {
-                            const uint32_t bo = 12u * OW * ci, br = 12u * ND * lsc;
-                            const uint32_t o = f_lo + br + (f_obm & (bo - br));
-                            const HA_AS_LDS char* P = (const HA_AS_LDS char*)Ob;
-                            const uint32_t o1 = o + f_st, o2 = o1 + f_st;
-                            j0n = *(const HA_AS_LDS float*)(P + o);
-                            j1n = *(const HA_AS_LDS float*)(P + o1);
-                            j2n = *(const HA_AS_LDS float*)(P + o2);
-                            y0n = *(const HA_AS_LDS float*)(P + (o + f_ly));
-                            y1n = *(const HA_AS_LDS float*)(P + (o1 + f_ly));
-                            y2n = *(const HA_AS_LDS float*)(P + (o2 + f_ly));
-                        }
+                    // robot lanes: the robot block of the contact's slot, in LDS (< KL), in the global spill rows, or
+                    // none. All of it comes from the contact's descriptor (one v_readlane: ci is wave-uniform): a lane
+                    // cuts its block offset out of the word at its own bit position
+                    const uint32_t w = (uint32_t)((CAP * NCH <= 64 || ci < 64) ? bcast_i((int)fd0, ci)
+                                                                                : bcast_i((int)fd1, ci - 64));
+                    const uint32_t fld = __builtin_amdgcn_ubfe(w, f_sh, 14u);
+                    // the LDS set, in every lane and under no lane mask. The lanes without an LDS entry for this contact
+                    // read the pad (a scalar mask chosen by the contact's bits): the robot lanes when it touches no link
+                    // or its robot block is in the spill rows. (Object lanes whose block is in the global row area read
+                    // the LDS object blocks at that offset: inside the rows, and replaced below)
+                    {
+                        const bool pad = lane_in((w & (FD_NL | FD_RG)) ? FM_NOB : FM_HI);
+                        const uint32_t o = pad ? f_pad : f_lo + fld;
+                        const uint32_t st = pad ? 0u : f_st, ly = pad ? 0u : f_ly;
+                        const uint32_t o1 = o + st, o2 = o1 + st;
+                        j0n = *(const HA_AS_LDS float*)(uintptr_t)o;
+                        j1n = *(const HA_AS_LDS float*)(uintptr_t)o1;
+                        j2n = *(const HA_AS_LDS float*)(uintptr_t)o2;
+                        y0n = *(const HA_AS_LDS float*)(uintptr_t)(o + ly);
+                        y1n = *(const HA_AS_LDS float*)(uintptr_t)(o1 + ly);
+                        y2n = *(const HA_AS_LDS float*)(uintptr_t)(o2 + ly);
                     }
-                    if (!lds_obj || rob_g) {
-                        if (f_ob ? !lds_obj : (f_rb && rob_g)) {
-                            const uint32_t bo = 12u * OW * ci, br = 12u * ND * (lsc - KL);
-                            const uint32_t o = f_go + br + (f_obm & (bo - br));
+                    // the global set: only for a contact with a global bit (wave-uniform: a scalar branch of its own, which
+                    // the empty statement keeps from merging into the lane mask below), in the lanes of that kind
+                    if (w & FD_GLB) {
+                        asm volatile("");
+                        if (w & (0x4000u << f_sh)) {
+                            const uint32_t o = f_go + fld;
                             const HA_AS_GLB char* G = (const HA_AS_GLB char*)c.spill;
                             const uint32_t o1 = o + f_st, o2 = o1 + f_st;
                             j0n = *(const HA_AS_GLB float*)(G + o);
@@ -831,6 +867,8 @@ HD void substep(SimCtx& c, float hdt) {
                     }
                     return;
                 }
+                int lsc = (CAP * NCH <= 64 || ci < 64) ? bcast_i(lsl0, ci) : bcast_i(lsl1, ci - 64);
+                bool lds_obj = LCH == NCH || ci < CAP * LCH;
                 if (lds_obj && lsc < KL) {
                     // every entry of this contact is in LDS: one set of six LDS loads from one base (the rows' J), each
                     // lane's block (object block of contact ci at stride OW, or robot block of slot lsc at stride ND)
