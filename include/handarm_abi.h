@@ -38,6 +38,9 @@
  *   ha_gather_obs                  compute_observations' torch.cat for a custom observation list
  *                                  (observable_vec_task.py:183-203)
  *   ha_render_camera               render_all_camera_sensors + camera image refresh (utils/camera.py:278-311)
+ *   ha_refresh_kinematics          gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor + refresh_jacobian_tensors /
+ *                                  refresh_mass_matrix_tensors (Isaac Gym tensor API; the hand_arm tasks do not call
+ *                                  them, Cartesian arm controllers written against that API do)
  * The fused entry points serve three tasks (ha_params_t.task): Ur5Sih (above), AllegroHand
  * (allegro_hand.py:586-633) and AllegroKuka (allegro_kuka_base.py:1355-1447).
  */
@@ -582,6 +585,22 @@ typedef struct ha_dr_replay_t {
     const float* dr_act_white;      /* [N][num_actions] */
 } ha_dr_replay_t;
 
+/* Additive v16 extension (no struct above changes, HA_ABI_VERSION stays 16): the robot's link Jacobians and joint-space
+ * inertia as tensors, computed from the bound dof_state (and, when dr_enable, the dr_scale link-mass rows) by a kernel
+ * of their own (csrc/ha_kinematics.h); the step kernels do not read them.
+ *   jacobian     [N][n_links][6][D]: for each selected link the linear velocity of its frame origin (rows 0..2, the point
+ *                of rigid_body_state[..., 0:3], not the COM) and its angular velocity (rows 3..5) per unit DOF velocity,
+ *                in the env frame: column d = (a_d x (p_link - o_d), a_d) for d an ancestor-or-self DOF of the link (a_d,
+ *                o_d the joint's world axis and anchor), 0 otherwise. Every element is written.
+ *   mass_matrix  [N][D][D]: the joint-space inertia the step uses, dof_armature on the diagonal, both triangles (exactly
+ *                symmetric). */
+typedef struct ha_kinematics_t {
+    float* jacobian;        /* [N][n_links][6][D] or NULL */
+    float* mass_matrix;     /* [N][D][D] or NULL */
+    const int32_t* links;   /* device, [n_links] link indices in 1..L-1; NULL = links 1..L-1 in order (n_links ignored) */
+    int32_t n_links;
+} ha_kinematics_t;
+
 typedef struct ha_handle_s* ha_handle;
 
 int ha_abi_version(void);
@@ -671,6 +690,11 @@ int ha_gather_obs(ha_handle h, const float* const* sources, const int32_t* strid
  * view_inv: the inverse view matrix (row-vector convention, 16 floats, host memory) the point cloud uses, as
  * camera.py:68 multiplies by view_mat.inverse(). Ur5Sih task only. */
 int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv, uint32_t flags, void* stream);
+/* Jacobian and mass-matrix tensors (see ha_kinematics_t) for all envs in one launch on `stream`, from the dof_state
+ * bound with ha_bind_state: gym.refresh_jacobian_tensors / refresh_mass_matrix_tensors. HA_E_ARG for a null handle or
+ * struct, for both outputs null, or for n_links outside 1..HA_MAX_LINKS when links is given; HA_E_STATE before
+ * ha_bind_state. A link index outside 1..L-1 in the device array yields all-zero rows. */
+int ha_refresh_kinematics(ha_handle h, const ha_kinematics_t* k, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 #include "ak_task.h"
 #include "ha_pointcloud.h"
 #include "ha_camera.h"
+#include "ha_kinematics.h"
 
 #define HA_ND 17         /* Ur5Sih DOF count (UR5 + SIH); AH_ND = 16 (Allegro) */
 
@@ -1640,6 +1641,27 @@ int ha_pointclouds(ha_handle h, const ha_pointcloud_t* pc, void* stream) {
     hipLaunchKernelGGL(ha_pointcloud_kernel, dim3(h->N), dim3(256), 0, s, L);
     HIPCHK(hipGetLastError());
     if (rec) (void)hipEventRecord(h->pc_ev[2 * h->pc_count++ + 1], s);
+    return HA_OK;
+}
+
+// Jacobian / mass-matrix tensors from the bound dof_state (ha_kinematics.h): one launch for whichever outputs are given
+int ha_refresh_kinematics(ha_handle h, const ha_kinematics_t* k, void* stream) {
+    if (!h || !k) return HA_E_ARG;
+    if (!k->jacobian && !k->mass_matrix) return HA_E_ARG;
+    if (k->links && (k->n_links < 1 || k->n_links > HA_MAX_LINKS)) return HA_E_ARG;
+    if (!h->bound) return HA_E_STATE;
+    KinLaunch a;
+    a.model = h->d_model;
+    a.dof_state = h->st.dof_state;
+    a.dr_scale = h->h_params.dr_enable ? h->st.dr_scale : nullptr;
+    a.jac = k->jacobian;
+    a.mm = k->mass_matrix;
+    a.links = k->links;
+    a.N = h->N;
+    a.K = !k->jacobian ? 0 : (k->links ? k->n_links : h->L - 1);
+    hipLaunchKernelGGL(ha_kinematics_kernel, dim3((h->N + HA_KIN_WAVES - 1) / HA_KIN_WAVES), dim3(64 * HA_KIN_WAVES),
+                       0, (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
     return HA_OK;
 }
 

@@ -10,8 +10,12 @@ Call sites this serves (under /root/reference/isaacgymenvs):
   gym.set_actor_root_state_tensor_indexed         tasks/hand_arm/task/multi_object_manipulation.py:89,118,167,228
   gym.set_dof_state_tensor_indexed                tasks/hand_arm/base/ur5sih.py:630
   gym.set_dof_position_target_tensor_indexed      ur5sih.py:626
-  gym.apply_rigid_body_force_tensors              tasks/allegro_kuka/allegro_kuka_base.py:1412-1414
+  gym.apply_rigid_body_force_tensors              tasks/allegro_kuka/allegro_kuka_base.py:1412-1414 (LOCAL_SPACE forces),
+                                                  :1417-1424 (privilegedActions: ENV_SPACE object torques)
   gym.acquire_dof_force_tensor / refresh          tasks/allegro_hand.py:151-152,409
+  gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor + refresh_jacobian_tensors / refresh_mass_matrix_tensors
+                                                  Isaac Gym's tensor API for Cartesian / operational-space arm
+                                                  controllers (no hand_arm call site; ha_refresh_kinematics)
 Isaac Gym returns bool from the set_* calls; so does this (a failing ABI call raises HandArmError
 instead of being silently ignored).
 """
@@ -19,6 +23,7 @@ import types
 
 import torch
 
+from . import model as HM
 from .sim import HandArmSim
 
 
@@ -85,22 +90,41 @@ class Gym:
     refresh_rigid_body_state_tensor = refresh_dof_state_tensor = refresh_net_contact_force_tensor = \
         refresh_dof_force_tensor = refresh_actor_root_state_tensor
 
-    def apply_rigid_body_force_tensors(self, sim, force_tensor=None, torque_tensor=None, space=gymapi.ENV_SPACE):
-        """Forces (N*B or N, B, 3) at the COM of the free objects for the next simulate call. LOCAL_SPACE
-        forces are rotated by the object's current orientation. Forces on robot links and torques are not
-        supported by the simulator (the reference applies neither on the hot path)."""
-        if torque_tensor is not None:
-            raise NotImplementedError("rigid-body torques are not supported")
-        if force_tensor is None:
-            return True
-        f = _t(force_tensor).view(sim.num_envs, sim.num_bodies, 3)
+    def acquire_jacobian_tensor(self, sim, name=None):
+        """(N, L-1, 6, D) of the robot, the only articulation (``name`` is accepted for signature compatibility)."""
+        return sim.acquire_jacobian_tensor()
+
+    def acquire_mass_matrix_tensor(self, sim, name=None):
+        return sim.acquire_mass_matrix_tensor()
+
+    def refresh_jacobian_tensors(self, sim):
+        sim.refresh_jacobian_tensors()
+
+    def refresh_mass_matrix_tensors(self, sim):
+        sim.refresh_mass_matrix_tensors()
+
+    @staticmethod
+    def _object_rows(sim, tensor, space):
+        """The free objects' rows of an (N*B or N, B, 3) rigid-body tensor, in the env frame."""
         o0, no = sim.model.body_object0, sim.n_obj
-        fo = f[:, o0:o0 + no, :]
+        v = _t(tensor).view(sim.num_envs, sim.num_bodies, 3)[:, o0:o0 + no, :]
         if space == gymapi.LOCAL_SPACE:
             a0 = sim.model.actor_object0
             q = sim.t["root_state"].view(sim.num_envs, sim.num_actors, 13)[:, a0:a0 + no, 3:7]
-            fo = _quat_rotate(q, fo)
-        sim.t["object_force"].view(sim.num_envs, no, 3).copy_(fo)
+            v = _quat_rotate(q, v)
+        return v
+
+    def apply_rigid_body_force_tensors(self, sim, force_tensor=None, torque_tensor=None, space=gymapi.ENV_SPACE):
+        """Forces at the COM of the free objects and torques on them (each N*B or N, B, 3; either may be None) for
+        the next simulate call. LOCAL_SPACE forces and torques are rotated by the object's current orientation.
+        Forces and torques on robot links are not supported by the simulator (the reference applies neither)."""
+        if torque_tensor is not None:
+            if "object_torque" in HM.null_fields(sim.task):
+                raise NotImplementedError(f"task {sim.task} binds no object_torque: rigid-body torques are not "
+                                          "supported for it")
+            sim.t["object_torque"].view(sim.num_envs, sim.n_obj, 3).copy_(self._object_rows(sim, torque_tensor, space))
+        if force_tensor is not None:
+            sim.t["object_force"].view(sim.num_envs, sim.n_obj, 3).copy_(self._object_rows(sim, force_tensor, space))
         return True
 
     def set_dof_position_target_tensor(self, sim, targets):

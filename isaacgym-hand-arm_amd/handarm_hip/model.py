@@ -261,6 +261,11 @@ class HaPointcloud(C.Structure):
                 ("flange_slot", C.c_int32)]
 
 
+class HaKinematics(C.Structure):
+    """ha_kinematics_t (include/handarm_abi.h, v16 extension): Jacobian / mass-matrix outputs (device pointers)."""
+    _fields_ = [("jacobian", P), ("mass_matrix", P), ("links", P), ("n_links", C.c_int32)]
+
+
 CAM_FROM_DEPTH = 1
 
 

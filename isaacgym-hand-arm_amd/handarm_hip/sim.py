@@ -6,6 +6,8 @@ semantics follow the Isaac Gym tensor API the hand_arm task calls (SURVEY.md §8
   acquire_actor_root_state_tensor / acquire_rigid_body_state_tensor / acquire_dof_state_tensor /
   acquire_net_contact_force_tensor   -> the live state tensors (zero-copy: they ARE the sim state)
   refresh_*                          -> no-ops (the kernels write the tensors in place)
+  acquire_jacobian_tensor / acquire_mass_matrix_tensor -> derived tensors, allocated on first use;
+  refresh_jacobian_tensors / refresh_mass_matrix_tensors -> one kernel launch from the current dof_state
   simulate(n)                        -> n gym.simulate() calls in ONE kernel launch
   set_actor_root_state_tensor_indexed / set_dof_state_tensor_indexed /
   set_dof_position_target_tensor(_indexed)  -> copy-in for the listed global actor indices (int32)
@@ -73,6 +75,9 @@ class HandArmSim:
             self.params.ah_object_rb_mass = self.model.pool_mass[self.params.ah_object_type]
         _lib.check(self.lib.ha_create(C.byref(self.model), C.byref(self.params), num_envs, C.byref(h)), "ha_create")
         self.h = h
+        # Jacobian / mass-matrix tensors (ha_refresh_kinematics), allocated by their acquire calls: derived from
+        # dof_state, not simulation state, so snapshot() / restore() leave them out (refresh after a restore)
+        self._jac = self._jac_key = self._jac_links = self._mm = None
         # contacts per substep the kernel family holds (clutter 84, Ur5Sih 21, AllegroKuka 21, AllegroHand 12)
         self.contact_capacity = int(self.lib.ha_contact_capacity(self.h))
         # persistent-manifold records per env (the contact_cache rows; zero = empty)
@@ -194,6 +199,56 @@ class HandArmSim:
     refresh_rigid_body_state_tensor = refresh_actor_root_state_tensor
     refresh_dof_state_tensor = refresh_actor_root_state_tensor
     refresh_net_contact_force_tensor = refresh_actor_root_state_tensor
+
+    def acquire_jacobian_tensor(self, links=None):
+        """gym.acquire_jacobian_tensor: (N, L-1, 6, D), Isaac Gym's fixed-base shape (the base link is omitted: model
+        link i is jac[:, i-1]); rows 0..2 the linear velocity of the link frame origin, 3..5 the angular velocity, env
+        frame. ``links`` (model link indices in 1..L-1): (N, len(links), 6, D) of those links only. Allocated and
+        filled for the current dof_state by the first call; later calls return the same tensor."""
+        key = None if links is None else tuple(int(i) for i in links)
+        if self._jac is not None:
+            if key != self._jac_key:
+                raise _lib.HandArmError("the Jacobian tensor was acquired with another link list")
+            return self._jac
+        if key is not None:
+            if not 1 <= len(key) <= HM.MAX_LINKS or any(not 1 <= i < self.num_links for i in key):
+                raise _lib.HandArmError(f"links must be 1..{HM.MAX_LINKS} link indices in 1..{self.num_links - 1}")
+            self._jac_links = torch.tensor(key, dtype=torch.int32, device=self.device)
+        k = self.num_links - 1 if key is None else len(key)
+        self._jac_key = key
+        self._jac = torch.zeros((self.num_envs, k, 6, self.num_dofs), dtype=torch.float32, device=self.device)
+        self._refresh_kinematics()
+        return self._jac
+
+    def acquire_mass_matrix_tensor(self):
+        """gym.acquire_mass_matrix_tensor: (N, D, D), the joint-space inertia the step uses (armature on the diagonal,
+        the env's DR link-mass scales when dr_enable). Allocated and filled by the first call."""
+        if self._mm is None:
+            self._mm = torch.zeros((self.num_envs, self.num_dofs, self.num_dofs), dtype=torch.float32,
+                                   device=self.device)
+            self._refresh_kinematics()
+        return self._mm
+
+    def _refresh_kinematics(self):
+        if self._jac is None and self._mm is None:
+            raise _lib.HandArmError("refresh before acquire_jacobian_tensor / acquire_mass_matrix_tensor")
+        k = HM.HaKinematics(self._jac.data_ptr() if self._jac is not None else None,
+                            self._mm.data_ptr() if self._mm is not None else None,
+                            self._jac_links.data_ptr() if self._jac_links is not None else None,
+                            len(self._jac_key) if self._jac_key is not None else 0)
+        _lib.check(self.lib.ha_refresh_kinematics(self.h, C.byref(k), self._stream()), "ha_refresh_kinematics")
+
+    def refresh_jacobian_tensors(self):
+        """One launch on the current stream; it writes the mass matrix too when that is acquired."""
+        if self._jac is None:
+            raise _lib.HandArmError("refresh_jacobian_tensors before acquire_jacobian_tensor")
+        self._refresh_kinematics()
+
+    def refresh_mass_matrix_tensors(self):
+        """One launch on the current stream; it writes the Jacobian too when that is acquired."""
+        if self._mm is None:
+            raise _lib.HandArmError("refresh_mass_matrix_tensors before acquire_mass_matrix_tensor")
+        self._refresh_kinematics()
 
     def simulate(self, n_calls=1, flags=0, env_ids=None):
         """gym.simulate n_calls times; env_ids (device tensor of distinct env indices): those envs only."""
