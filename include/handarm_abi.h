@@ -41,6 +41,8 @@
  *   ha_refresh_kinematics          gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor + refresh_jacobian_tensors /
  *                                  refresh_mass_matrix_tensors (Isaac Gym tensor API; the hand_arm tasks do not call
  *                                  them, Cartesian arm controllers written against that API do)
+ *   ha_refresh_contacts            gym.get_rigid_contacts / get_env_rigid_contacts (the contact list of the bound state as
+ *                                  a tensor; no hand_arm call site: tactile observations, grasp diagnostics)
  * The fused entry points serve three tasks (ha_params_t.task): Ur5Sih (above), AllegroHand
  * (allegro_hand.py:586-633) and AllegroKuka (allegro_kuka_base.py:1355-1447).
  */
@@ -601,6 +603,33 @@ typedef struct ha_kinematics_t {
     int32_t n_links;
 } ha_kinematics_t;
 
+/* Additive v16 extension (no struct above changes, HA_ABI_VERSION stays 16): the contacts the narrow phase finds for
+ * the bound state, as a tensor, from a kernel of their own per family (csrc/handarm_hip.hip contacts_body); the step
+ * kernels do not read it. These are the contacts detect() produces for the bound root_state, dof_state, object_indices,
+ * object_scale, dr_scale and collision_enabled: FK first, persistent manifolds off, the family's own capacity
+ * (ha_contact_capacity) and replacement rule (over capacity the shallowest stored contact gives way), in the order the
+ * step's contact list has. The launch writes contacts and counts only: no bound tensor, contact_cache, contact_stats,
+ * object_force / object_torque or separating-face record changes.
+ * Row (HA_CONTACT_REC floats, 80 bytes, so rows are 16-byte aligned when the tensor is):
+ *   0..2    x, env frame, midway between the two surface points
+ *   3..5    n, the unit normal from body b to body a
+ *   6       sep (negative: penetration)
+ *   7, 8    body codes a, b: -1 static or ground, 0..n_objects-1 object, 100 + link
+ *   9, 10   body0, body1: the rigid_body_state row of a and of b (body_object0 + o, body_robot0 + link), -1 for a static
+ *   11..13  the surface point on a, x + n sep / 2, in a's frame (link frame from the launch's FK; object origin frame
+ *           from its root_state row; the env frame for a static)
+ *   14..16  the surface point on b, x - n sep / 2, in b's frame
+ *   17..19  0, reserved
+ * Rows >= counts[env][0] are not written. */
+#define HA_CONTACT_REC 20
+typedef struct ha_contacts_t {
+    float*   contacts;       /* [N][max_contacts][HA_CONTACT_REC], 16-byte aligned */
+    int32_t* counts;         /* [N][2]: contacts kept, contacts offered */
+    int32_t  max_contacts;   /* >= ha_contact_capacity(h) */
+    const int32_t* env_ids;  /* device, n_envs distinct env indices; NULL = every env (n_envs ignored) */
+    int32_t  n_envs;
+} ha_contacts_t;
+
 typedef struct ha_handle_s* ha_handle;
 
 int ha_abi_version(void);
@@ -695,6 +724,11 @@ int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv,
  * struct, for both outputs null, or for n_links outside 1..HA_MAX_LINKS when links is given; HA_E_STATE before
  * ha_bind_state. A link index outside 1..L-1 in the device array yields all-zero rows. */
 int ha_refresh_kinematics(ha_handle h, const ha_kinematics_t* k, void* stream);
+/* The contact tensor (see ha_contacts_t) in one launch on `stream`, one workgroup per env or per listed env (env indices
+ * outside 0..N-1 are skipped): gym.get_rigid_contacts. The launch follows neither ha_set_env_order nor
+ * ha_enable_kernel_timing. HA_E_ARG for a null handle or struct, null or misaligned contacts, null counts,
+ * max_contacts < ha_contact_capacity(h), or env_ids with n_envs < 1; HA_E_STATE before ha_bind_state. */
+int ha_refresh_contacts(ha_handle h, const ha_contacts_t* c, void* stream);
 
 #ifdef __cplusplus
 }

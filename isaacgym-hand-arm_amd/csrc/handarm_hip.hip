@@ -800,6 +800,134 @@ static env_kernel_t kernel_for(int fam, int mode) {
     }
 }
 
+// ----------------------------------------------------------------------------- contact query
+// ha_refresh_contacts: the contact list detect() produces for the bound state, as rows of HA_CONTACT_REC floats (layout
+// in include/handarm_abi.h). One kernel per family; a body of its own beside env_body, so the step kernels' text does
+// not change. The env block is the family's own (task_lds_bytes, the offsets env_body uses): detect reads the
+// narrow-phase scratch through col_view inside the phase union, the object slots and the contact list follow it; the
+// rows, M and S regions stay unused. The overflow families' entries past chunk 0 go to the env's off_ct region of the
+// global area, which is scratch within a substep (every substep's detect rewrites it before reading it).
+// What must not change: pcm, pairf and selfc are null (no manifold record and no separating-face record is read or
+// written; results do not depend on the face records), load_env takes no force, and nothing is stored back.
+
+// frame of body code `code` (env frame for a static): its rigid_body_state row and the point p in that frame
+__device__ __forceinline__ f3 contact_local(const SimCtx& c, int code, f3 p, float& body) {
+    const EnvLDS& s = *c.s;
+    if (code < 0) {
+        body = -1.0f;
+        return p;
+    }
+    PoseF P;
+    if (code >= 100) {
+        P = PoseF{ld3(s.lp[code - 100]), ldq(s.lq[code - 100])};
+        body = (float)(c.m->body_robot0 + code - 100);
+    } else {
+        P = object_pose(c, code);       // the origin pose, as object_state computes it
+        body = (float)(c.m->body_object0 + code);
+    }
+    return qrot(qf{-P.q.x, -P.q.y, -P.q.z, P.q.w}, p - P.p);
+}
+
+template <int FAM>
+__device__ __forceinline__ void contacts_body(const ha_model_t* __restrict__ model, const ha_params_t* __restrict__ params,
+                                              const ha_state_t& st, int num_envs, float* __restrict__ spill,
+                                              const int32_t* __restrict__ env_ids, float* __restrict__ contacts,
+                                              int32_t* __restrict__ counts, int max_contacts) {
+    constexpr int NCH = task_contact_chunks<FAM>();
+    using PC = FamPhys<FAM>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
+    if (env < 0 || env >= num_envs) return;
+    SimCtx c;
+    c.gather = false;
+#ifdef HA_AB_TIMING
+    c.dry = false;
+#endif
+    c.m = model;
+    c.p = params;
+    c.s = reinterpret_cast<EnvLDS*>(smem);
+    c.Minv = reinterpret_cast<float*>(smem + minv_lds_offset<PC>());
+    c.col = col_view<PC>(&c.s->u);
+    c.o = reinterpret_cast<ObjLDS*>(smem + obj_lds_offset<PC>());
+    c.k = reinterpret_cast<ContactLDS*>(smem + contact_lds_offset<PC>());
+    c.spill = PC::ovf ? spill + (size_t)env * PC::spill_floats : nullptr;
+    c.selfc = nullptr;
+    c.pairf = nullptr;
+    c.selfm = PC::selfc ? reinterpret_cast<uint32_t*>(smem + selfm_lds_offset<PC>()) : nullptr;
+    c.sepf = 0xFF;
+    c.pcm = nullptr;
+    c.pslot = -1;
+    c.pkind = c.pA = c.pB = 0;
+    c.pemit = 0;
+#ifdef HA_PROFILE
+    c.pk = 0;
+    c.pcls = 0;
+#endif
+    c.act_in = nullptr;
+    c.obs_out = nullptr;
+    c.clip_act = c.clip_obs = 0.0f;
+    c.maxc = PC::cap * NCH;
+    c.kg = PC::ovf ? reinterpret_cast<ContactLDS*>(c.spill + PC::off_ct) : nullptr;
+    c.kc0 = PC::ovf ? PC::cap : PC::cap * NCH;
+    c.lane = threadIdx.x;
+    c.D = task_nd<FAM>();
+    c.NO = params->n_objects;
+    c.L = model->n_links;
+    c.dr = (params->dr_enable && st.dr_scale) ? st.dr_scale + (size_t)env * HA_DR_SIZE : nullptr;
+    c.drg = nullptr;
+    c.rp = nullptr;
+    c.last = false;
+    load_env(c, st, env, false);
+    fk(c);
+    detect<PC::selfc>(c);               // zeroes nc / noff itself and ends on a wsync
+    const EnvLDS& s = *c.s;
+    int nc = __builtin_amdgcn_readfirstlane(s.nc);
+    nc = nc < c.maxc ? nc : c.maxc;
+    nc = nc < max_contacts ? nc : max_contacts;     // the host entry checks max_contacts >= the capacity
+    float* out = contacts + (size_t)env * max_contacts * HA_CONTACT_REC;
+    // lane i: contacts i and i + 64 (the capacity is at most 128); five 16-byte stores per 80-byte row
+    static_assert(PC::cap * NCH <= 128, "two contacts per lane");
+    for (int ci = c.lane; ci < nc; ci += 64) {
+        ContactLDS k = ct_get(c, ci);
+        f3 x = ld3(k.x), n = ld3(k.n);
+        f3 h = n * (0.5f * k.sep);
+        float b0, b1;
+        f3 la = contact_local(c, k.a, x + h, b0);
+        f3 lb = contact_local(c, k.b, x - h, b1);
+        float4* r = reinterpret_cast<float4*>(out + (size_t)ci * HA_CONTACT_REC);
+        r[0] = make_float4(x.x, x.y, x.z, n.x);
+        r[1] = make_float4(n.y, n.z, k.sep, (float)k.a);
+        r[2] = make_float4((float)k.b, b0, b1, la.x);
+        r[3] = make_float4(la.y, la.z, lb.x, lb.y);
+        r[4] = make_float4(lb.z, 0.0f, 0.0f, 0.0f);
+    }
+    if (c.lane == 0) {
+        counts[2 * (size_t)env] = nc;
+        counts[2 * (size_t)env + 1] = s.noff;
+    }
+}
+#define HA_CONTACTS_KERNEL(name, FAM)                                                                           \
+    extern "C" __global__ void __launch_bounds__(64)                                                          \
+        name(const ha_model_t* __restrict__ model, const ha_params_t* __restrict__ params, ha_state_t st,       \
+             int num_envs, float* spill, const int32_t* env_ids, float* contacts, int32_t* counts,              \
+             int max_contacts) {                                                                                \
+        contacts_body<FAM>(model, params, st, num_envs, spill, env_ids, contacts, counts, max_contacts);       \
+    }
+HA_CONTACTS_KERNEL(ha_contacts_kernel, HA_TASK_UR5SIH)
+HA_CONTACTS_KERNEL(hb_contacts_kernel, FAM_UR5SIH_CLUTTER)
+HA_CONTACTS_KERNEL(ah_contacts_kernel, HA_TASK_ALLEGRO_HAND)
+HA_CONTACTS_KERNEL(ak_contacts_kernel, HA_TASK_ALLEGRO_KUKA)
+typedef void (*contacts_kernel_t)(const ha_model_t*, const ha_params_t*, ha_state_t, int, float*, const int32_t*, float*,
+                                  int32_t*, int);
+static contacts_kernel_t contacts_kernel_for(int fam) {
+    switch (fam) {
+        case FAM_UR5SIH_CLUTTER: return hb_contacts_kernel;
+        case HA_TASK_ALLEGRO_HAND: return ah_contacts_kernel;
+        case HA_TASK_ALLEGRO_KUKA: return ak_contacts_kernel;
+        default: return ha_contacts_kernel;
+    }
+}
+
 // ----------------------------------------------------------------------------- indexed setters
 extern "C" __global__ void ha_copy_indexed_kernel(float* dst, const float* src, const int32_t* idx, int n, int row,
                                                   int rows_per_index) {
@@ -1184,6 +1312,8 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
     for (int mode : {MODE_STEP, MODE_SIMULATE, MODE_OBSERVE, MODE_RESET})
         HIPCHK(hipFuncSetAttribute((const void*)kernel_for(h->fam, mode), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds_bytes(h->fam)));
+    HIPCHK(hipFuncSetAttribute((const void*)contacts_kernel_for(h->fam), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lds_bytes(h->fam)));
     HIPCHK(hipEventCreate(&h->ev0));
     HIPCHK(hipEventCreate(&h->ev1));
     *out = h;
@@ -1661,6 +1791,21 @@ int ha_refresh_kinematics(ha_handle h, const ha_kinematics_t* k, void* stream) {
     a.K = !k->jacobian ? 0 : (k->links ? k->n_links : h->L - 1);
     hipLaunchKernelGGL(ha_kinematics_kernel, dim3((h->N + HA_KIN_WAVES - 1) / HA_KIN_WAVES), dim3(64 * HA_KIN_WAVES),
                        0, (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
+    return HA_OK;
+}
+
+// The contact tensor of the bound state (contacts_body): one workgroup per env, or per listed env. Identity order or the
+// caller's list (not ha_set_env_order's), and no timing record: the launch is not a physics launch
+int ha_refresh_contacts(ha_handle h, const ha_contacts_t* c, void* stream) {
+    if (!h || !c) return HA_E_ARG;
+    if (!c->contacts || !c->counts || ((uintptr_t)c->contacts & 15)) return HA_E_ARG;
+    if (c->max_contacts < contact_capacity(h->fam)) return HA_E_ARG;
+    if (c->env_ids && (c->n_envs < 1 || c->n_envs > h->N)) return HA_E_ARG;
+    if (!h->bound) return HA_E_STATE;
+    hipLaunchKernelGGL(contacts_kernel_for(h->fam), dim3(c->env_ids ? c->n_envs : h->N), dim3(64), lds_bytes(h->fam),
+                       (hipStream_t)stream, h->d_model, h->d_params, h->st, h->N, h->d_spill, c->env_ids, c->contacts,
+                       c->counts, c->max_contacts);
     HIPCHK(hipGetLastError());
     return HA_OK;
 }

@@ -16,11 +16,14 @@ Call sites this serves (under /root/reference/isaacgymenvs):
   gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor + refresh_jacobian_tensors / refresh_mass_matrix_tensors
                                                   Isaac Gym's tensor API for Cartesian / operational-space arm
                                                   controllers (no hand_arm call site; ha_refresh_kinematics)
+  gym.get_rigid_contacts / get_env_rigid_contacts the contact list of the current state (no hand_arm call site: tactile
+                                                  observations, grasp diagnostics; ha_refresh_contacts)
 Isaac Gym returns bool from the set_* calls; so does this (a failing ABI call raises HandArmError
 instead of being silently ignored).
 """
 import types
 
+import numpy as np
 import torch
 
 from . import model as HM
@@ -52,6 +55,34 @@ def _quat_rotate(q, v):
 
 def _t(x):
     return x.tensor if isinstance(x, _Unwrapped) else x
+
+
+# Isaac Gym's RigidContact fields that the contact query computes. lambda, friction, offset0 / offset1 and initialOverlap
+# are left out rather than zero-filled: the query solves nothing
+RIGID_CONTACT_DTYPE = np.dtype([("env0", np.int32), ("env1", np.int32), ("body0", np.int32), ("body1", np.int32),
+                                ("localPos0", np.float32, (3,)), ("localPos1", np.float32, (3,)),
+                                ("minDist", np.float32), ("normal", np.float32, (3,))])
+
+
+def rigid_contacts_from_rows(rows, counts, env0=0):
+    """Contact tensor rows (n, cap, 20) and counts (n, 2) or (n,) as numpy arrays -> one RIGID_CONTACT_DTYPE record per
+    kept contact (rows < counts[e, 0] of env e, env by env in list order). env0 / env1: env0 + e; body0 / body1: the
+    rigid_body_state rows of the two bodies within their env (-1: a static or the ground); localPos0 / localPos1: the
+    surface points in the bodies' frames (env frame for a static); minDist: the separation (negative: penetration);
+    normal: unit, from body1 to body0, env frame."""
+    rows = np.asarray(rows, np.float32)
+    kept = np.asarray(counts).reshape(rows.shape[0], -1)[:, 0].astype(np.int64)
+    if rows.ndim != 3 or rows.shape[2] != HM.CONTACT_REC or (kept < 0).any() or (kept > rows.shape[1]).any():
+        raise ValueError("rows must be (n, cap, 20) and 0 <= counts[:, 0] <= cap")
+    env, slot = np.nonzero(np.arange(rows.shape[1])[None, :] < kept[:, None])
+    r = rows[env, slot]
+    out = np.zeros(len(r), RIGID_CONTACT_DTYPE)
+    out["env0"] = out["env1"] = env + env0
+    out["body0"], out["body1"] = r[:, 9], r[:, 10]
+    out["localPos0"], out["localPos1"] = r[:, 11:14], r[:, 14:17]
+    out["minDist"] = r[:, 6]
+    out["normal"] = r[:, 3:6]
+    return out
 
 
 class Gym:
@@ -102,6 +133,32 @@ class Gym:
 
     def refresh_mass_matrix_tensors(self, sim):
         sim.refresh_mass_matrix_tensors()
+
+    def acquire_contact_tensor(self, sim):
+        """(contacts (N, capacity, 20), counts (N, 2)): the tensor form of get_rigid_contacts (no Isaac Gym counterpart;
+        row layout in include/handarm_abi.h, ha_contacts_t)."""
+        return sim.acquire_contact_tensor()
+
+    def refresh_contact_tensor(self, sim):
+        sim.refresh_contact_tensor()
+
+    def get_rigid_contacts(self, sim):
+        """gym.get_rigid_contacts(sim): the contacts of the current state of all envs as a numpy structured array with
+        Isaac Gym's RigidContact field names (RIGID_CONTACT_DTYPE; body indices are per env, the normal points from
+        body1 to body0). One query launch, then a device synchronisation and a copy to the host."""
+        rows, counts = sim.acquire_contact_tensor()
+        sim.refresh_contact_tensor()
+        return rigid_contacts_from_rows(rows.cpu().numpy(), counts.cpu().numpy())
+
+    def get_env_rigid_contacts(self, sim, env_index):
+        """gym.get_env_rigid_contacts for one env. Isaac Gym's call takes an env handle; this binding has no env
+        handles, so it takes the sim and the env's index. Only that env is queried."""
+        e = int(env_index)
+        if not 0 <= e < sim.num_envs:
+            raise IndexError(f"env_index {e} outside 0..{sim.num_envs - 1}")
+        rows, counts = sim.acquire_contact_tensor()
+        sim.refresh_contact_tensor(torch.tensor([e], dtype=torch.int32, device=sim.device))
+        return rigid_contacts_from_rows(rows[e:e + 1].cpu().numpy(), counts[e:e + 1].cpu().numpy(), env0=e)
 
     @staticmethod
     def _object_rows(sim, tensor, space):

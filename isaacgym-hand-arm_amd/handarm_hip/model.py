@@ -266,6 +266,14 @@ class HaKinematics(C.Structure):
     _fields_ = [("jacobian", P), ("mass_matrix", P), ("links", P), ("n_links", C.c_int32)]
 
 
+CONTACT_REC = 20     # HA_CONTACT_REC: floats per row of the contact tensor
+
+
+class HaContacts(C.Structure):
+    """ha_contacts_t (include/handarm_abi.h, v16 extension): the contact tensor and its counts (device pointers)."""
+    _fields_ = [("contacts", P), ("counts", P), ("max_contacts", C.c_int32), ("env_ids", P), ("n_envs", C.c_int32)]
+
+
 CAM_FROM_DEPTH = 1
 
 

@@ -8,6 +8,8 @@ semantics follow the Isaac Gym tensor API the hand_arm task calls (SURVEY.md §8
   refresh_*                          -> no-ops (the kernels write the tensors in place)
   acquire_jacobian_tensor / acquire_mass_matrix_tensor -> derived tensors, allocated on first use;
   refresh_jacobian_tensors / refresh_mass_matrix_tensors -> one kernel launch from the current dof_state
+  acquire_contact_tensor / refresh_contact_tensor -> the narrow phase's contact list of the current state (derived
+                                        too; one query launch that changes no state; gym.get_rigid_contacts)
   simulate(n)                        -> n gym.simulate() calls in ONE kernel launch
   set_actor_root_state_tensor_indexed / set_dof_state_tensor_indexed /
   set_dof_position_target_tensor(_indexed)  -> copy-in for the listed global actor indices (int32)
@@ -78,6 +80,8 @@ class HandArmSim:
         # Jacobian / mass-matrix tensors (ha_refresh_kinematics), allocated by their acquire calls: derived from
         # dof_state, not simulation state, so snapshot() / restore() leave them out (refresh after a restore)
         self._jac = self._jac_key = self._jac_links = self._mm = None
+        # contact tensor and counts (ha_refresh_contacts), allocated by acquire_contact_tensor: derived too
+        self._contacts = self._contact_counts = None
         # contacts per substep the kernel family holds (clutter 84, Ur5Sih 21, AllegroKuka 21, AllegroHand 12)
         self.contact_capacity = int(self.lib.ha_contact_capacity(self.h))
         # persistent-manifold records per env (the contact_cache rows; zero = empty)
@@ -249,6 +253,30 @@ class HandArmSim:
         if self._mm is None:
             raise _lib.HandArmError("refresh_mass_matrix_tensors before acquire_mass_matrix_tensor")
         self._refresh_kinematics()
+
+    def acquire_contact_tensor(self):
+        """The contacts of the current state as tensors: ``(contacts (N, contact_capacity, 20) float32, counts (N, 2)
+        int32)``. Row layout in include/handarm_abi.h (ha_contacts_t): x, n (from body b to body a), sep, the body
+        codes, the rigid_body_state rows of both bodies and the two surface points in their bodies' frames.
+        counts[:, 0] rows of an env are valid (the rest keep what they held), counts[:, 1] is what the narrow phase
+        offered. Allocated and filled for the current state by the first call; later calls return the same tensors."""
+        if self._contacts is None:
+            self._contacts = torch.zeros((self.num_envs, self.contact_capacity, HM.CONTACT_REC), dtype=torch.float32,
+                                         device=self.device)
+            self._contact_counts = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=self.device)
+            self.refresh_contact_tensor()
+        return self._contacts, self._contact_counts
+
+    def refresh_contact_tensor(self, env_ids=None):
+        """One launch on the current stream: FK and the narrow phase on the bound state (persistent manifolds off),
+        writing only the contact tensor and its counts. env_ids (int32 device tensor of distinct env indices): those
+        envs only, the others' rows and counts stay."""
+        if self._contacts is None:
+            raise _lib.HandArmError("refresh_contact_tensor before acquire_contact_tensor")
+        ids = None if env_ids is None else env_ids.to(device=self.device, dtype=torch.int32).contiguous()
+        k = HM.HaContacts(self._contacts.data_ptr(), self._contact_counts.data_ptr(), self._contacts.shape[1],
+                          ids.data_ptr() if ids is not None else None, int(ids.numel()) if ids is not None else 0)
+        _lib.check(self.lib.ha_refresh_contacts(self.h, C.byref(k), self._stream()), "ha_refresh_contacts")
 
     def simulate(self, n_calls=1, flags=0, env_ids=None):
         """gym.simulate n_calls times; env_ids (device tensor of distinct env indices): those envs only."""
