@@ -294,3 +294,26 @@ def place_cuboid_edge_on_link(st, model, body_state, link, pen=0.0003):
         rs[e, model.actor_object0, 7:13] = 0.0
     st["object_force"][:] = 0.0
     return st
+
+
+def kuka_closed_hand_scene(sim, hs, lo, up, seed=0):
+    """The fingers half closed (40-80% of their range) with their targets at the upper limits and the cuboid in the
+    palm (palm_offset from iiwa7_link_7, allegro_kuka_base.py:1430-1436), still: the grasp the C2 bench reaches late in
+    its episodes (offered up to 45 contacts per substep): cube-finger, cube-palm and finger-finger contacts at once"""
+    from oracle.oracle_lib import Oracle
+    from oracle import f32
+    n, p, m = sim.num_envs, sim.params, sim.model
+    fill_kuka_scene(hs, n, lo, up, list(p.reset_pose), hs["object_scale"].copy(), list(m.table_pos), seed=4)
+    rng = np.random.default_rng(seed)
+    ds = hs["dof_state"].reshape(n, 23, 2)
+    ds[:, 7:, 0] = lo[7:] + (up[7:] - lo[7:]) * rng.uniform(0.4, 0.8, (n, 16)).astype(np.float32)
+    ds[:, :, 1] = 0
+    hs["sim_targets"][:] = ds[..., 0]
+    hs["sim_targets"][:, 7:] = up[7:]
+    probe = hs.copy()
+    Oracle(m, p, n).simulate(probe, 1)
+    palm = probe["rigid_body_state"].reshape(n, m.n_bodies, 13)[:, m.body_robot0 + p.ak_palm_link]
+    off = np.broadcast_to(np.array(p.ak_palm_offset, np.float32), (n, 3))
+    rs = hs["root_state"].reshape(n, m.n_actors, 13)
+    rs[:, m.actor_object0, 0:3] = palm[:, 0:3] + f32.qrot(palm[:, 3:7], off) + rng.uniform(-0.01, 0.01, (n, 3))
+    rs[:, m.actor_object0, 7:13] = 0

@@ -1,7 +1,8 @@
 """The independent float64 contact checker (tests/contact_ref.py) on the C oracle's contact rows: three
 box piles (every property, including pair completeness and axis quality against a brute-force SAT) and two YCB-hull
-piles (unit normals, depth and surface points). It pins the oracle; tests/test_gpu_contact_tensor.py runs the same
-checker on the kernel's rows."""
+piles (unit normals, depth and surface points), and the rows with a robot link of three hand scenes (the Ur5Sih pile in
+the hand, the AllegroHand closing hand, the AllegroKuka closed hand) against the link hulls posed by the independent
+FK. It pins the oracle; tests/test_gpu_contact_tensor.py runs the same checker on the kernel's rows."""
 import numpy as np
 import pytest
 
@@ -51,3 +52,13 @@ def test_ycb_piles_on_the_oracle(seed, near_hand):
     print(f"ycb pile seed {seed}: {rep}")
     assert rep.rows > 300
     CR.assert_report(rep, margin=None, pairs=False)
+
+
+@pytest.mark.parametrize("name", list(CR.LINK_SCENES))
+def test_link_hull_rows_on_the_oracle(name):
+    """Link-object, link-static and link-link rows of the three robots against the link hulls posed by the independent
+    float64 FK: (a), (b), the lower bound of (c), no row of a link without a hull or of a filtered link pair."""
+    make, n = CR.LINK_SCENES[name]
+    scene, m, p, st = make(n)
+    orc = Oracle(m, p, n)
+    CR.check_link_scene(name, scene, m, p, st, lambda e: orc.contacts(st, e))

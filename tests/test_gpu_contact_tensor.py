@@ -61,26 +61,13 @@ def assert_rows_match(sim, st, tag):
 
 # ----------------------------------------------------------------------------- the four families' states
 def ur5sih_pile():
-    """The pile-in-hand state of tests/test_gpu_overflow.py (seed 13): the three objects dropped together into the
-    closed hand just above the table."""
+    """The pile-in-hand state (tests/contact_ref.py ur5sih_hand_pile) on a sim."""
     need_gpu()
     from handarm_hip.sim import HandArmSim
-    from oracle.oracle_lib import HostState, Oracle
     n = 64
+    st = CR.ur5sih_hand_pile(n)[3]
     sim = HandArmSim(n, "cuda:0")
     assert sim.contact_capacity == 84
-    st = HostState(n)
-    scenes.fill_scene(st, n, seed=13, near_hand=0.0)
-    probe = st.copy()
-    Oracle(sim.model, sim.params, n).simulate(probe, 1)
-    body = probe["rigid_body_state"].reshape(n, 34, 13)
-    rng = np.random.default_rng(13)
-    hull_links = sorted({int(sim.model.hull_link[k]) for k in range(sim.model.n_link_hulls)})
-    rs = st["root_state"].reshape(n, 6, 13)
-    for o in range(3):
-        lk = np.array(hull_links)[rng.integers(len(hull_links) // 2, len(hull_links), n)]
-        rs[:, 3 + o, 0:3] = body[np.arange(n), sim.model.body_robot0 + lk, 0:3] + rng.uniform(-0.015, 0.015, (n, 3))
-        rs[:, 3 + o, 7:13] = 0.0
     push(sim, st)
     return sim, st
 
@@ -88,15 +75,10 @@ def ur5sih_pile():
 def allegro_closing_hand():
     need_gpu()
     from handarm_hip.sim import HandArmSim
-    from oracle.oracle_lib import HostState
     n = 128
+    st = CR.allegro_closing_hand(n)[3]
     sim = HandArmSim(n, "cuda:0", task=HM.TASK_ALLEGRO_HAND)
     assert sim.contact_capacity == 48
-    lo = np.array(sim.model.dof_lower[:16], np.float32)
-    up = np.array(sim.model.dof_upper[:16], np.float32)
-    st = HostState(n, model=sim.model, params=sim.params)
-    scenes.fill_allegro_scene(st, n, lo, up, seed=0)
-    st["sim_targets"][:] = up
     push(sim, st)
     return sim, st
 
@@ -104,16 +86,10 @@ def allegro_closing_hand():
 def kuka_closed_hand(n=128):
     need_gpu()
     from handarm_hip.sim import HandArmSim
-    from oracle.oracle_lib import HostState
-    from tests.test_gpu_fused_steps import kuka_closed_hand_scene
+    st = CR.kuka_closed_hand(n)[3]
     sim = HandArmSim(n, "cuda:0", task=HM.TASK_ALLEGRO_KUKA)
     assert sim.contact_capacity == 42
-    lo = np.array(sim.model.dof_lower[:23], np.float32)
-    up = np.array(sim.model.dof_upper[:23], np.float32)
-    st = HostState(n, model=sim.model, params=sim.params)
-    st["object_scale"][:] = sim.t["object_scale"].cpu().numpy()
-    kuka_closed_hand_scene(sim, st, lo, up)
-    st["contact_stats"][:] = 0
+    assert (st["object_scale"] == sim.t["object_scale"].cpu().numpy().reshape(st["object_scale"].shape)).all()
     push(sim, st)
     return sim, st
 
@@ -334,6 +310,19 @@ def test_float64_checker_on_the_kernels_rows(box_sim, seed):
     print(f"box pile seed {seed} (kernel rows): {rep}")
     assert rep.rows > 1000 and rep.pairs == 6 * n
     CR.assert_report(rep, margin=float(sim.params.contact_margin))
+
+
+@pytest.mark.parametrize("name", list(CR.LINK_SCENES))
+def test_float64_checker_on_the_kernels_link_rows(name):
+    """Link-object, link-static and link-link rows of the kernel against the link hulls posed by the independent FK."""
+    need_gpu()
+    from handarm_hip.sim import HandArmSim
+    make, n = CR.LINK_SCENES[name]
+    scene, m, p, st = make(n)
+    sim = HandArmSim(n, "cuda:0", task=int(p.task))
+    push(sim, st)
+    rows, counts = query(sim)
+    CR.check_link_scene(name, scene, sim.model, sim.params, st, lambda e: rows[e, :counts[e, 0]], tag=" (kernel rows)")
 
 
 # ----------------------------------------------------------------------------- 6. errors

@@ -16,6 +16,7 @@ import torch
 from handarm_hip import model as HM
 from oracle import kuka_oracle as KO
 from tests import scenes, step_chains
+from tests.scenes import kuka_closed_hand_scene  # noqa: F401  (other test modules import it from here)
 
 pytestmark = pytest.mark.gpu
 K = 3
@@ -226,29 +227,6 @@ def test_kuka_throw_fused_step_with_physics_matches_oracle_chain():
     assert fired == 0 and sim.model.n_static == 14
     g = stats_match(sim, hs, "kuka throw")
     assert (g[:, 3] > 0).mean() > 0.9, "contacts with the bucket pieces in most envs"
-
-
-def kuka_closed_hand_scene(sim, hs, lo, up, seed=0):
-    """The fingers half closed (40-80% of their range) with their targets at the upper limits and the cuboid in the
-    palm (palm_offset from iiwa7_link_7, allegro_kuka_base.py:1430-1436), still: the grasp the C2 bench reaches late in
-    its episodes (offered up to 45 contacts per substep): cube-finger, cube-palm and finger-finger contacts at once"""
-    from oracle.oracle_lib import Oracle
-    from oracle import f32
-    n, p, m = sim.num_envs, sim.params, sim.model
-    _kuka_random_scene(sim, hs, lo, up)
-    rng = np.random.default_rng(seed)
-    ds = hs["dof_state"].reshape(n, 23, 2)
-    ds[:, 7:, 0] = lo[7:] + (up[7:] - lo[7:]) * rng.uniform(0.4, 0.8, (n, 16)).astype(np.float32)
-    ds[:, :, 1] = 0
-    hs["sim_targets"][:] = ds[..., 0]
-    hs["sim_targets"][:, 7:] = up[7:]
-    probe = hs.copy()
-    Oracle(m, p, n).simulate(probe, 1)
-    palm = probe["rigid_body_state"].reshape(n, m.n_bodies, 13)[:, m.body_robot0 + p.ak_palm_link]
-    off = np.broadcast_to(np.array(p.ak_palm_offset, np.float32), (n, 3))
-    rs = hs["root_state"].reshape(n, m.n_actors, 13)
-    rs[:, m.actor_object0, 0:3] = palm[:, 0:3] + f32.qrot(palm[:, 3:7], off) + rng.uniform(-0.01, 0.01, (n, 3))
-    rs[:, m.actor_object0, 7:13] = 0
 
 
 def test_kuka_fused_step_closed_hand_overflows_chunk0_and_matches_oracle_chain():
