@@ -43,6 +43,8 @@
  *                                  them, Cartesian arm controllers written against that API do)
  *   ha_refresh_contacts            gym.get_rigid_contacts / get_env_rigid_contacts (the contact list of the bound state as
  *                                  a tensor; no hand_arm call site: tactile observations, grasp diagnostics)
+ *   ha_cartesian_targets           no Isaac Gym counterpart: the damped least-squares Cartesian controller its users write
+ *                                  in torch on the Jacobian tensor, as one launch that writes joint position targets
  * The fused entry points serve three tasks (ha_params_t.task): Ur5Sih (above), AllegroHand
  * (allegro_hand.py:586-633) and AllegroKuka (allegro_kuka_base.py:1355-1447).
  */
@@ -630,6 +632,33 @@ typedef struct ha_contacts_t {
     int32_t  n_envs;
 } ha_contacts_t;
 
+/* Additive v16 extension (no struct above changes, HA_ABI_VERSION stays 16): a Cartesian controller for one link of the
+ * robot, from a kernel of its own (csrc/ha_cartesian.h); the step kernels do not read it. Per launched env, from the
+ * bound dof_state: FK, the tool point p_t = p_link + R_link offset, the task error e (6 floats, env frame), the 6 x D
+ * Jacobian of the tool point over the link's ancestor-or-self DOFs selected by dof_mask, and one damped least-squares
+ * step dq = J^T (J J^T + damping^2 I)^-1 e, written as targets[env][d] = clamp(q_d + dq_d, dof_lower[d], dof_upper[d])
+ * for those DOFs only; every other element of targets keeps its value.
+ *   mode HA_CART_POSE   goal row = pos(3) + quat xyzw(4) of the tool frame in the env frame: e[0:3] = pos - p_t, e[3:6] the
+ *                       rotation vector of quat (normalised) x conj(q_link), shortest arc
+ *   mode HA_CART_DELTA  goal row = e itself (6 floats: Isaac Gym examples' dpose)
+ *   position_only != 0  e[3:6] and the angular rows of J are zeroed (fingertip position commands)
+ *   max_step > 0        the whole dq is scaled so that max_d |dq_d| <= max_step (the direction is kept)
+ *   null_gain > 0       posture term: dq += (I - J^T (J J^T + damping^2 I)^-1 J) z, z_d = null_gain (q_rest[d] - q_d) on the
+ *                       selected DOFs. The damped projector is not exact: it leaks damping^2 (J J^T + damping^2 I)^-1 J z
+ *                       into task space, so a loop with the posture term settles millimetres off the goal. */
+#define HA_CART_POSE 0
+#define HA_CART_DELTA 1
+typedef struct ha_cartesian_t {
+    const float* goal;        /* device: [n][7] (HA_CART_POSE) or [n][6] (HA_CART_DELTA), n = n_envs or N, row k for the k-th listed env */
+    float* targets;           /* device [N][D]: the tensor the caller hands to ha_set_dof_position_target (may be the bound sim_targets) */
+    float* err_out;           /* device [N][6] or NULL */
+    const float* q_rest;      /* device [D] or NULL */
+    const int32_t* env_ids;   /* device or NULL = all envs; indices outside 0..N-1 are skipped */
+    int32_t n_envs, link, mode, position_only;
+    uint32_t dof_mask;
+    float offset[3], damping, max_step, null_gain;
+} ha_cartesian_t;
+
 typedef struct ha_handle_s* ha_handle;
 
 int ha_abi_version(void);
@@ -729,6 +758,13 @@ int ha_refresh_kinematics(ha_handle h, const ha_kinematics_t* k, void* stream);
  * ha_enable_kernel_timing. HA_E_ARG for a null handle or struct, null or misaligned contacts, null counts,
  * max_contacts < ha_contact_capacity(h), or env_ids with n_envs < 1; HA_E_STATE before ha_bind_state. */
 int ha_refresh_contacts(ha_handle h, const ha_contacts_t* c, void* stream);
+/* One damped least-squares step of the Cartesian controller (see ha_cartesian_t) in one launch on `stream`, one
+ * wavefront per env or per listed env. Like ha_refresh_contacts the launch follows neither ha_set_env_order nor
+ * ha_enable_kernel_timing; it reads the bound dof_state and writes targets and err_out only. HA_E_ARG for a null handle,
+ * struct, goal or targets, link outside 1..L-1, an unknown mode, damping not finite or <= 0, max_step or null_gain
+ * negative or not finite, null_gain > 0 with q_rest null, a dof_mask without an ancestor-or-self DOF of link, or env_ids
+ * with n_envs < 1; HA_E_STATE before ha_bind_state. */
+int ha_cartesian_targets(ha_handle h, const ha_cartesian_t* c, void* stream);
 
 #ifdef __cplusplus
 }

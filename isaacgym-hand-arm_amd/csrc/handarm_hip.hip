@@ -13,6 +13,7 @@
 #include "ha_pointcloud.h"
 #include "ha_camera.h"
 #include "ha_kinematics.h"
+#include "ha_cartesian.h"
 
 #define HA_ND 17         /* Ur5Sih DOF count (UR5 + SIH); AH_ND = 16 (Allegro) */
 
@@ -1043,6 +1044,9 @@ struct ha_handle_s {
     ha_dr_replay_t h_drr;     // ha_bind_dr_replay: the caller's buffers (host copy; drr_bound 0: none)
     ha_dr_replay_t* d_drr;    // and the device copy the kernels read under HA_FLAG_REPLAY_DR
     int drr_bound;
+    // ha_cartesian_targets: per link its ancestor-or-self DOFs, the links from the base to it, and its depth
+    uint32_t link_dofs[HA_MAX_LINKS], link_path[HA_MAX_LINKS];
+    int link_depth[HA_MAX_LINKS];
 };
 
 #define HIPCHK(x)                                                                     \
@@ -1282,6 +1286,14 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
     h->fam = fam;
     h->h_params = *params;
     h->stat_slots = 1;
+    // links come after their parents (the FK's levels rely on it too), so one pass fills the per-link chains
+    for (int i = 0; i < model->n_links; i++) {
+        int par = model->link_parent[i], d = model->link_dof[i];
+        bool child = i > 0 && par >= 0 && par < i;
+        h->link_dofs[i] = (child ? h->link_dofs[par] : 0u) | (d >= 0 && d < model->n_dofs ? 1u << d : 0u);
+        h->link_path[i] = (child ? h->link_path[par] : 0u) | (1u << i);
+        h->link_depth[i] = model->link_level[i];
+    }
     // the broad phase's pairs must fit the family's separating-face records (one byte each in the env's global area)
     {
         int NO = params->n_objects, NS = model->n_static, NLH = model->n_link_hulls;
@@ -1806,6 +1818,46 @@ int ha_refresh_contacts(ha_handle h, const ha_contacts_t* c, void* stream) {
     hipLaunchKernelGGL(contacts_kernel_for(h->fam), dim3(c->env_ids ? c->n_envs : h->N), dim3(64), lds_bytes(h->fam),
                        (hipStream_t)stream, h->d_model, h->d_params, h->st, h->N, h->d_spill, c->env_ids, c->contacts,
                        c->counts, c->max_contacts);
+    HIPCHK(hipGetLastError());
+    return HA_OK;
+}
+
+// One damped least-squares step of the Cartesian controller (ha_cartesian.h): one wavefront per env, or per listed env.
+// Identity order or the caller's list, no timing record; the link's DOF chain is checked here, where the model is
+int ha_cartesian_targets(ha_handle h, const ha_cartesian_t* c, void* stream) {
+    if (!h || !c || !c->goal || !c->targets) return HA_E_ARG;
+    if (c->link < 1 || c->link >= h->L) return HA_E_ARG;
+    if (c->mode != HA_CART_POSE && c->mode != HA_CART_DELTA) return HA_E_ARG;
+    // x - x is 0 for a finite x and NaN for an infinity or a NaN, so each comparison is false for those
+    if (!(c->damping - c->damping == 0.0f && c->damping > 0.0f)) return HA_E_ARG;
+    if (!(c->max_step - c->max_step == 0.0f && c->max_step >= 0.0f)) return HA_E_ARG;
+    if (!(c->null_gain - c->null_gain == 0.0f && c->null_gain >= 0.0f)) return HA_E_ARG;
+    if (c->null_gain > 0.0f && !c->q_rest) return HA_E_ARG;
+    if (!(h->link_dofs[c->link] & c->dof_mask)) return HA_E_ARG;
+    if (c->env_ids && c->n_envs < 1) return HA_E_ARG;
+    if (!h->bound) return HA_E_STATE;
+    CartLaunch a;
+    a.model = h->d_model;
+    a.dof_state = h->st.dof_state;
+    a.goal = c->goal;
+    a.targets = c->targets;
+    a.err_out = c->err_out;
+    a.q_rest = c->null_gain > 0.0f ? c->q_rest : nullptr;
+    a.env_ids = c->env_ids;
+    a.N = h->N;
+    a.n = c->env_ids ? c->n_envs : h->N;
+    a.link = c->link;
+    a.depth = h->link_depth[c->link];
+    a.mode = c->mode;
+    a.position_only = c->position_only != 0;
+    a.path = h->link_path[c->link];
+    a.dofs = h->link_dofs[c->link] & c->dof_mask;
+    for (int k = 0; k < 3; k++) a.off[k] = c->offset[k];
+    a.lam2 = c->damping * c->damping;
+    a.max_step = c->max_step;
+    a.null_gain = c->null_gain;
+    hipLaunchKernelGGL(ha_cartesian_kernel, dim3((a.n + HA_KIN_WAVES - 1) / HA_KIN_WAVES), dim3(64 * HA_KIN_WAVES), 0,
+                       (hipStream_t)stream, a);
     HIPCHK(hipGetLastError());
     return HA_OK;
 }

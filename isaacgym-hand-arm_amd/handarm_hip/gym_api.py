@@ -142,6 +142,15 @@ class Gym:
     def refresh_contact_tensor(self, sim):
         sim.refresh_contact_tensor()
 
+    def set_cartesian_pose_target(self, sim, controller, goal):
+        """Isaac Gym has no counterpart: one step of a handarm_hip.controllers.CartesianController of this sim (one
+        launch that writes the joint position targets the next gym.simulate drives to), here so that code written
+        against this namespace need not leave it. goal: (N, 7) pos + quat xyzw, or (N, 6) in "delta" mode."""
+        if controller.sim is not sim:
+            raise ValueError("the controller belongs to another sim")
+        controller.step(_t(goal))
+        return True
+
     def get_rigid_contacts(self, sim):
         """gym.get_rigid_contacts(sim): the contacts of the current state of all envs as a numpy structured array with
         Isaac Gym's RigidContact field names (RIGID_CONTACT_DTYPE; body indices are per env, the normal points from

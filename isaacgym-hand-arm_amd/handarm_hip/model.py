@@ -274,6 +274,16 @@ class HaContacts(C.Structure):
     _fields_ = [("contacts", P), ("counts", P), ("max_contacts", C.c_int32), ("env_ids", P), ("n_envs", C.c_int32)]
 
 
+CART_POSE, CART_DELTA = 0, 1     # HA_CART_POSE / HA_CART_DELTA
+
+
+class HaCartesian(C.Structure):
+    """ha_cartesian_t (include/handarm_abi.h, v16 extension): one launch of the Cartesian controller (device pointers)."""
+    _fields_ = [("goal", P), ("targets", P), ("err_out", P), ("q_rest", P), ("env_ids", P), ("n_envs", C.c_int32),
+                ("link", C.c_int32), ("mode", C.c_int32), ("position_only", C.c_int32), ("dof_mask", C.c_uint32),
+                ("offset", C.c_float * 3), ("damping", C.c_float), ("max_step", C.c_float), ("null_gain", C.c_float)]
+
+
 CAM_FROM_DEPTH = 1
 
 

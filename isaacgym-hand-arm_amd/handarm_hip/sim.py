@@ -278,6 +278,75 @@ class HandArmSim:
                           ids.data_ptr() if ids is not None else None, int(ids.numel()) if ids is not None else 0)
         _lib.check(self.lib.ha_refresh_contacts(self.h, C.byref(k), self._stream()), "ha_refresh_contacts")
 
+    def link_index(self, link):
+        """Model link index of ``link``: an index, or the scene's link name (KeyError when the scene has none such)."""
+        if isinstance(link, str):
+            names = [l["name"] for l in self.scene["robot"]["links"]]
+            if link not in names:
+                raise KeyError(f"the scene has no link named {link!r}")
+            return names.index(link)
+        return int(link)
+
+    def link_dofs(self, link):
+        """The ancestor-or-self DOF indices of a model link, ascending."""
+        i, out = int(link), []
+        while 0 <= i < self.num_links:
+            if self.model.link_dof[i] >= 0:
+                out.append(int(self.model.link_dof[i]))
+            i = self.model.link_parent[i] if i > 0 else -1
+        return sorted(out)
+
+    def cartesian_targets(self, goal, link, dofs=None, mode="pose", offset=(0.0, 0.0, 0.0), damping=0.05, max_step=0.0,
+                          q_rest=None, null_gain=0.0, position_only=False, targets=None, err_out=None, env_ids=None):
+        """One damped least-squares step of a Cartesian controller for ``link`` (index or scene link name), in one launch
+        on the current stream and without a host sync (ha_cartesian_targets; no Isaac Gym counterpart):
+        ``targets[env, d] = clamp(q + J^T (J J^T + damping^2 I)^-1 e, lower, upper)`` on ``dofs`` (DOF indices, default
+        every ancestor DOF of the link; the others of them are held), every other element of ``targets`` untouched.
+        goal: float32 device tensor, (n, 7) tool pose pos + quat xyzw in the env frame (mode "pose") or (n, 6) the task
+        error itself (mode "delta"), n = num_envs or len(env_ids), row k for the k-th listed env. offset: the tool point
+        in the link frame. max_step > 0 limits max |dq|. q_rest (D floats) with null_gain > 0 adds the posture term
+        through the damped null-space projector, which leaks into task space: such a loop settles millimetres off the
+        goal. position_only drops the orientation rows (fingertips). targets defaults to the bound sim_targets, the
+        tensor the next simulate() drives to; err_out (N, 6) receives e. Returns targets."""
+        if isinstance(mode, str):
+            if mode not in ("pose", "delta"):
+                raise _lib.HandArmError(f"mode must be 'pose' or 'delta', not {mode!r}")
+            mode = HM.CART_POSE if mode == "pose" else HM.CART_DELTA
+        mode = int(mode)                   # HM.CART_*: the library checks the value
+        li = self.link_index(link)
+        mask = 0
+        for d in (self.link_dofs(li) if dofs is None else dofs):
+            if not 0 <= int(d) < self.num_dofs:
+                raise _lib.HandArmError(f"DOF index {d} outside 0..{self.num_dofs - 1}")
+            mask |= 1 << int(d)
+        ids = None if env_ids is None else env_ids.to(device=self.device, dtype=torch.int32).contiguous()
+        n = self.num_envs if ids is None else int(ids.numel())
+        if n < 1:
+            raise _lib.HandArmError("env_ids is empty")
+        width = 6 if mode == HM.CART_DELTA else 7
+
+        def dev(x, shape, what):
+            if x is None:
+                return None
+            x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+            if tuple(x.shape) != shape or not x.is_contiguous():
+                raise _lib.HandArmError(f"{what} must be a contiguous float32 tensor of shape {shape}")
+            return x
+        goal = dev(goal, (n, width), "goal")
+        targets = dev(self.t["sim_targets"] if targets is None else targets, (self.num_envs, self.num_dofs), "targets")
+        err_out = dev(err_out, (self.num_envs, 6), "err_out")
+        q_rest = dev(q_rest, (self.num_dofs,), "q_rest")
+        c = HM.HaCartesian(goal.data_ptr() if goal is not None else None, targets.data_ptr(),
+                           err_out.data_ptr() if err_out is not None else None,
+                           q_rest.data_ptr() if q_rest is not None else None,
+                           ids.data_ptr() if ids is not None else None, n if ids is not None else 0, li, mode,
+                           int(bool(position_only)), mask, (C.c_float * 3)(*[float(v) for v in offset]),
+                           float(damping), float(max_step), float(null_gain))
+        _lib.check(self.lib.ha_cartesian_targets(self.h, C.byref(c), self._stream()), "ha_cartesian_targets")
+        # the launch reads these asynchronously: hold them until the next call replaces them
+        self._cart_hold = (goal, q_rest, ids)
+        return targets
+
     def simulate(self, n_calls=1, flags=0, env_ids=None):
         """gym.simulate n_calls times; env_ids (device tensor of distinct env indices): those envs only."""
         if env_ids is None:
