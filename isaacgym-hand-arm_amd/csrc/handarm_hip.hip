@@ -14,191 +14,9 @@
 #include "ha_camera.h"
 #include "ha_kinematics.h"
 #include "ha_cartesian.h"
-
-#define HA_ND 17         /* Ur5Sih DOF count (UR5 + SIH); AH_ND = 16 (Allegro) */
+#include "ha_family.h"   /* Family<FAM>: every per-family constant; FamPhys<FAM>, pair_slots */
 
 enum { MODE_SIMULATE = 0, MODE_STEP = 1, MODE_OBSERVE = 2, MODE_RESET = 3 };
-
-// Kernel families: one per task, plus the Ur5Sih clutter family (bin-picking, BASELINE config 5: up to 8
-// objects, two contact chunks, a 65-coordinate velocity) that runs the same Ur5Sih task math. ha_create
-// picks the family from the task and the object count.
-#define FAM_UR5SIH_CLUTTER 3
-template <int FAM>
-__host__ __device__ constexpr int fam_task() { return FAM == FAM_UR5SIH_CLUTTER ? HA_TASK_UR5SIH : FAM; }
-template <int FAM>
-__host__ __device__ constexpr int task_nd() {
-    return FAM == HA_TASK_ALLEGRO_HAND ? AH_ND : (FAM == HA_TASK_ALLEGRO_KUKA ? AK_ND : HA_ND);
-}
-// object slots in LDS per env (objects per env the family's kernels support)
-template <int FAM>
-__host__ __device__ constexpr int task_obj_capacity() {
-    return FAM == FAM_UR5SIH_CLUTTER ? HA_MAX_OBJ : (FAM == HA_TASK_UR5SIH ? 3 : 1);
-}
-// contact chunks (MAXC contacts each). The clutter family holds 84 contacts per substep: a settled 8-object bin
-// offers 59 on average and at most ~90 (bench contact_stats), 42 were at capacity in 99% of substeps.
-#ifndef HB_CHUNKS
-#define HB_CHUNKS 4
-#endif
-// clutter chunks whose object-block rows stay in LDS (0..4); the rest go to the env's global row area, which the
-// PGS reads one contact ahead. 0: env block 16.8 KB, 9 workgroups per CU (1: 22.0 KB, 7 per CU): C5 shard
-// 23.0 -> 19.5 ms (tools/ab_variants.sh binpick)
-#ifndef HB_LDS_CHUNKS
-#define HB_LDS_CHUNKS 0
-#endif
-// Ur5Sih (3 objects) and AllegroHand: overflow chunks (PhysCfg OVF). Chunk 0 keeps the one-chunk LDS layout (21 /
-// 12 contacts); the further chunks' contact entries, rows and row constants live in the env's global area, touched
-// only by substeps with more contacts than chunk 0 holds. Round 3 measured C4 over 21 contacts in 5.4% of the
-// substeps of a whole episode (per-env maximum 57 at p99) and C3 over 12 in 3.2% (maximum 41)
-#ifndef HA_CHUNKS
-#define HA_CHUNKS 4
-#endif
-#ifndef HA_AH_CHUNKS
-#define HA_AH_CHUNKS 4
-#endif
-// AllegroKuka: with the hand's self-collision (v12) a substep offers 12 contacts on average and up to ~50 under random
-// actions; chunk 0 holds 21 in LDS, a second chunk in the env's global area takes the rest
-#ifndef HA_AK_CHUNKS
-#define HA_AK_CHUNKS 2
-#endif
-template <int FAM>
-__host__ __device__ constexpr int task_contact_chunks() {
-    return FAM == FAM_UR5SIH_CLUTTER ? HB_CHUNKS
-           : (FAM == HA_TASK_UR5SIH ? HA_CHUNKS : (FAM == HA_TASK_ALLEGRO_HAND ? HA_AH_CHUNKS : HA_AK_CHUNKS));
-}
-template <int FAM>
-__host__ __device__ constexpr bool task_overflow() { return FAM != FAM_UR5SIH_CLUTTER; }
-// persistent contact manifolds (v13) are compiled into every family but AllegroHand: with them its kernel needs 76 B/lane
-// of register spills (44 without) and measured 4.8 -> 5.0 ms per C3 step with twice the HBM traffic; its hand closes on
-// the cube and on itself every step, so few of its pairs keep a record long enough to pay back
-template <int FAM>
-__host__ __device__ constexpr bool task_pcm() { return FAM != HA_TASK_ALLEGRO_HAND; }
-static inline bool family_pcm(int fam) { return fam != HA_TASK_ALLEGRO_HAND; }
-// clutter family: 1 recomputes the object blocks of the contact rows in registers from the contact entries in the
-// rows phase and at every PGS fetch (PhysCfg RC) instead of storing them in the env's global row area. Measured on
-// C5 (round 3): 22.1 -> 30.8 ms per step, the ~140 VALU per fetch cost more than the stored rows' traffic, which the
-// one-contact-ahead prefetch hides; the product keeps the stored rows
-#ifndef HB_RECOMPUTE
-#define HB_RECOMPUTE 0
-#endif
-// clutter family: the contacts that touch no robot link are solved in packed passes (four contacts on disjoint objects
-// per pass, one per 16-lane row) instead of one whole-wave contact block after another (PhysCfg PACK);
-// the oracle follows the same order for the configurations this family runs (physics_oracle.c packed_pgs)
-#ifndef HB_PACKED_PGS
-#define HB_PACKED_PGS 1
-#endif
-// the Ur5Sih 3-object family can pack the substeps whose contacts fit chunk 0 (<= 21: rows in LDS, the constants per
-// contact in PK, the rest serial over the overflow chunks): measured off. Three objects give passes of at most three
-// contacts, a bench env offers ~12 of which ~4 objects' worth share an object, so a sweep still runs ~4-5 passes of
-// ~2-3 contacts, each slower than the serial block it replaces: C4 shard 3.14 -> 3.60 ms per step (r5j-r5p,
-// bit-identical; with lane-permuted constants 3.69 ms). A -DHA_PACKED_PGS=1 build needs the oracle's h->packed = 1
-#ifndef HA_PACKED_PGS
-#define HA_PACKED_PGS 0
-#endif
-// clutter family: link contacts whose robot blocks stay in LDS (the rest use the global spill rows). 2 slots
-// keep the env block at <= 20 KB, i.e. 8 workgroups per CU (8 slots: 22.8 KB, 7 per CU)
-#ifndef HB_LINK_SLOTS
-#define HB_LINK_SLOTS 2
-#endif
-// the Ur5Sih 3-object family's LDS link slots (split rows, HA_SPLIT_ABOVE_OCAP): 4 put the env block at 13.5 KB,
-// 12 workgroups per CU (8 slots: 15.1 KB, 10 per CU): C4 shard 5.24 -> 5.01 ms; more link contacts use the
-// global spill rows (tests/test_gpu_parity.py::test_link_contacts_spill_rows_match_oracle)
-#ifndef HA_LINK_SLOTS
-#define HA_LINK_SLOTS 4
-#endif
-// minimum waves per SIMD asked of the Ur5Sih (3-object) kernels' register allocation: 3 (<= 168 VGPRs; 149
-// without spills now) so the VGPRs allow the 12 workgroups per CU the LDS does
-#ifndef HA_WAVES_PER_EU
-#define HA_WAVES_PER_EU 3
-#endif
-// AllegroKuka / AllegroHand (one dense chunk): contacts per substep, and waves per SIMD asked of their
-// register allocation. 12 contacts put the env block at 13.6 KB of LDS and 3 waves per SIMD cap the kernels at
-// 168 VGPRs (84 / 72 B/lane scratch), so 12 workgroups run per CU instead of 8 (LDS 20.1 / 16.6 KB, 193
-// VGPRs): C2 0.705 -> 0.652 ms, C3 3.23 -> 2.70 ms (tools/ab_variants.sh). The list is then over capacity in
-// 1.3% (C2) / 2.0% (C3) of substeps, where the shallowest contacts give way (bench contact_stats).
-// AllegroKuka holds a full chunk (21) since round 3: with 2 LDS link slots its rows still fit in front of S in the
-// phase union (9.3 KB env block, 16 workgroups per CU); C2 over capacity 1.3% -> 0.09% of substeps for +2.7%
-// step time. AllegroHand stays at 12: 21 in the compact layout cost +9% (0.12%), the dense rows do not fit.
-// Waves per SIMD: AllegroKuka asks for 3 since round 5 (168 VGPRs, 8 B/lane scratch): with the self pass and the
-// persistent manifolds it needed 120 B/lane of spills at 4, whose scratch write-backs were 43% of its HBM traffic
-// (48.8 -> 27.8 KB per env) and cost more than the fourth wave won (C2 kernel 1.064 -> 1.043 ms,
-// tools/diag/ab_traffic.sh); AllegroHand stays at 4 (16384 envs: the fourth wave per SIMD is worth 10% there).
-#ifndef HA_AK_CONTACTS
-#define HA_AK_CONTACTS 21
-#endif
-#ifndef HA_AH_CONTACTS
-#define HA_AH_CONTACTS 12
-#endif
-#ifndef HA_AK_WAVES_PER_EU
-#define HA_AK_WAVES_PER_EU 3
-#endif
-#ifndef HA_AH_WAVES_PER_EU
-#define HA_AH_WAVES_PER_EU 4
-#endif
-template <int FAM>
-__host__ __device__ constexpr int task_chunk_capacity() {
-    return FAM == HA_TASK_ALLEGRO_KUKA ? HA_AK_CONTACTS : (FAM == HA_TASK_ALLEGRO_HAND ? HA_AH_CONTACTS : MAXC);
-}
-#ifndef HB_WAVES_PER_EU
-#define HB_WAVES_PER_EU 3
-#endif
-template <int FAM>
-__host__ __device__ constexpr int task_waves_per_eu() {
-    return FAM == HA_TASK_UR5SIH ? HA_WAVES_PER_EU
-           : (FAM == HA_TASK_ALLEGRO_KUKA ? HA_AK_WAVES_PER_EU
-                                          : (FAM == HA_TASK_ALLEGRO_HAND ? HA_AH_WAVES_PER_EU : HB_WAVES_PER_EU));
-}
-// largest hull a family's narrow-phase scratch holds: the YCB pool hulls have up to 64 vertices and 124 face
-// planes; the Allegro scenes' hulls (cooked to <= 32 vertices, <= 60 planes) take half, which puts the
-// AllegroHand env block at 10.2 KB: 16 workgroups per CU with 4 waves per SIMD
-template <int FAM>
-__host__ __device__ constexpr int task_col_verts() { return (FAM == HA_TASK_ALLEGRO_KUKA || FAM == HA_TASK_ALLEGRO_HAND) ? 32 : 64; }
-template <int FAM>
-__host__ __device__ constexpr int task_col_planes() { return (FAM == HA_TASK_ALLEGRO_KUKA || FAM == HA_TASK_ALLEGRO_HAND) ? 64 : 124; }
-// AllegroKuka env block (PhysCfg SPLIT / NG / MU): split rows with HA_AK_LINK_SLOTS link contacts in LDS, no
-// compound-object gather buffer (its one object is a cuboid; ha_create enforces one hull per pool object) and
-// S ~ M^-1 inside the phase union: 13.3 -> 9.1 KB, so 16 workgroups per CU hold the 4096 envs of config C2 in
-// one round (12 per CU ran them in 1.33 rounds). HA_AK_COMPACT=0 restores the round-2 layout (A/B timing).
-#ifndef HA_AK_COMPACT
-#define HA_AK_COMPACT 1
-#endif
-// (3 in round 4: with the hand's self contacts most contacts touch links. 9 since round 5: at 3 waves per SIMD the
-// CU holds 12 workgroups, so the LDS may grow to 13.3 KB per env (552 B per slot; 9 is the most that keeps 12 per CU).
-// A/B on C2 (profiles/README.md): 3 slots 1.037 ms / 27.8 KB HBM per env, 6 slots 1.018 ms / 20.5 KB, 9 slots
-// 1.015 ms / 14.5 KB)
-#ifndef HA_AK_LINK_SLOTS
-#define HA_AK_LINK_SLOTS 9
-#endif
-// AllegroHand in the same compact layout (split rows, no gather buffer, S in the union): every AllegroHand contact
-// touches a finger link, so its rows are robot blocks in HA_AH_LINK_SLOTS LDS slots and the global spill rows
-#ifndef HA_AH_COMPACT
-#define HA_AH_COMPACT 0
-#endif
-#ifndef HA_AH_LINK_SLOTS
-#define HA_AH_LINK_SLOTS 5
-#endif
-template <int FAM>
-__host__ __device__ constexpr bool task_compact() {
-    return (FAM == HA_TASK_ALLEGRO_KUKA && HA_AK_COMPACT) || (FAM == HA_TASK_ALLEGRO_HAND && HA_AH_COMPACT);
-}
-template <int FAM>
-__host__ __device__ constexpr int task_link_slots() {
-    return FAM == FAM_UR5SIH_CLUTTER ? HB_LINK_SLOTS
-                                     : (!task_compact<FAM>() ? HA_LINK_SLOTS
-                                                              : (FAM == HA_TASK_ALLEGRO_KUKA ? HA_AK_LINK_SLOTS : HA_AH_LINK_SLOTS));
-}
-template <int FAM>
-using FamPhys = PhysCfg<task_nd<FAM>(), task_obj_capacity<FAM>(), task_contact_chunks<FAM>(), task_link_slots<FAM>(),
-                        FAM == FAM_UR5SIH_CLUTTER ? HB_LDS_CHUNKS : task_contact_chunks<FAM>(),
-                        task_chunk_capacity<FAM>(), task_col_verts<FAM>(), task_col_planes<FAM>(),
-                        task_compact<FAM>() ? 1 : -1, task_compact<FAM>() ? 0 : HA_MAX_GATHER, task_compact<FAM>(),
-                        FAM == FAM_UR5SIH_CLUTTER && HB_RECOMPUTE, task_overflow<FAM>(),
-#ifdef HA_X_NO_SELF     /* A/B timing builds only: the Allegro families without their self-collision pass */
-                        false,
-#else
-                        FAM == HA_TASK_ALLEGRO_HAND || FAM == HA_TASK_ALLEGRO_KUKA,
-#endif
-                        (FAM == FAM_UR5SIH_CLUTTER && HB_PACKED_PGS) || (FAM == HA_TASK_UR5SIH && HA_PACKED_PGS)>;
-
 
 // ----------------------------------------------------------------------------- state load/store
 // Generic over the env layout in ha_model_t (actor / rigid-body creation order of the task).
@@ -519,20 +337,14 @@ __device__ __forceinline__ void ak_extras(const SimCtx& c, const ha_state_t& S, 
     }
 }
 
-template <int FAM, int MODE>
-__device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, const ha_params_t* __restrict__ params,
-                                         const ha_state_t& st, int num_envs, int n_calls, uint32_t flags,
-                                         int stat_slot, float* __restrict__ spill,
-                                         const int32_t* __restrict__ env_ids, const StepIO& io) {
-    constexpr int TASK = fam_task<FAM>();
-    constexpr int ND = task_nd<FAM>();
-    constexpr int NCH = task_contact_chunks<FAM>();
-    using PC = FamPhys<FAM>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    // one workgroup per env; ha_simulate_envs launches one per listed env
-    int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
-    if (env < 0 || env >= num_envs) return;
-    SimCtx c;
+// The SimCtx fields every per-env body sets the same way: the views into the env's LDS block (task_lds_bytes<PC>), the
+// env's global area (`area`; null: the family has none, or the body uses none of it) with the overflow chunks' contact
+// entries in it, the contact capacity, lane and sizes, the env's DR row, and the pair cursor at rest. The caller sets
+// what differs between the bodies: selfc, pairf, pcm, the step I/O, drg and rp.
+template <class PC>
+__device__ __forceinline__ void sim_ctx_init(SimCtx& c, const ha_model_t* __restrict__ model,
+                                             const ha_params_t* __restrict__ params, const ha_state_t& st, int env,
+                                             char* smem, float* area) {
     c.gather = false;
 #ifdef HA_AB_TIMING
     c.dry = false;
@@ -544,52 +356,65 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
     c.col = col_view<PC>(&c.s->u);
     c.o = reinterpret_cast<ObjLDS*>(smem + obj_lds_offset<PC>());
     c.k = reinterpret_cast<ContactLDS*>(smem + contact_lds_offset<PC>());
-    c.spill = (PC::split || PC::ovf || PC::selfc) ? spill + (size_t)env * PC::spill_floats : nullptr;
-    c.selfc = PC::selfc ? reinterpret_cast<uint8_t*>(c.spill + PC::off_selfc) : nullptr;
-    // separating-face records of the broad phase's pairs: the clutter family only. There most candidate object pairs in
-    // the bin are apart (5.8 narrow phases a substep, 0.2 with contacts) and each needs a fresh hull setup; with the
-    // records 4.8 of them are skipped (narrow phases 13.8% -> 2.2% of the substep, checks 5.9%). In the Allegro
-    // families the separated pairs are link hulls against the cube, whose side is cached across consecutive pairs so
-    // the narrow phase's sphere cull is cheaper than a record check (C3: checks 6.8% for 3.5% saved), and the record
-    // register cost spills (tools/phase_profile.py, r5l)
-    c.pairf = (c.spill && FAM == FAM_UR5SIH_CLUTTER) ? reinterpret_cast<uint8_t*>(c.spill + PC::off_pairf) : nullptr;
-#ifdef HA_X_NO_PAIRF    /* A/B builds only: no separating-face records for the broad phase's pairs */
-    c.pairf = nullptr;
-#endif
+    c.spill = area;
     c.selfm = PC::selfc ? reinterpret_cast<uint32_t*>(smem + selfm_lds_offset<PC>()) : nullptr;
     c.sepf = 0xFF;
-    // persistent contact manifolds (ha_params_t v13): the env's records, when the caller bound the buffer and the
-    // tolerance is on; slots = detect's pairs (per object: ground, statics, later objects, link hulls; link hulls x
-    // statics) + the self pairs (ha_contact_cache_slots)
-    {
-        int NO = params->n_objects, NS = model->n_static, NLH = model->n_link_hulls;
-        size_t slots = (size_t)NO * (1 + NS + NLH) + (size_t)(NO * (NO - 1) / 2) + (size_t)NLH * NS + model->n_self_pairs;
-        c.pcm = (st.contact_cache && params->pcm_lin_tol > 0.0f) ? st.contact_cache + (size_t)env * slots * HA_PCM_REC
-                                                                   : nullptr;
-    }
-    if constexpr (!task_pcm<FAM>()) c.pcm = nullptr;
-#ifdef HA_X_NO_PCM     /* A/B builds only: the persistent-manifold code compiled out */
-    c.pcm = nullptr;
-#endif
     c.pslot = -1;
     c.pkind = c.pA = c.pB = 0;
     c.pemit = 0;
 #ifdef HA_PROFILE
     c.pcls = 0;
 #endif
+    c.maxc = PC::cap * PC::nch;
+    // overflow chunks: contact entries past chunk 0 in the env's global area (null otherwise: ct_global folds away)
+    c.kg = PC::ovf ? reinterpret_cast<ContactLDS*>(c.spill + PC::off_ct) : nullptr;
+    c.kc0 = PC::ovf ? PC::cap : PC::cap * PC::nch;
+    c.lane = threadIdx.x;
+    c.D = PC::nd;                 // == model->n_dofs (ha_create); a constant, so loops over D unroll
+    c.NO = params->n_objects;
+    c.L = model->n_links;
+    c.dr = (params->dr_enable && st.dr_scale) ? st.dr_scale + (size_t)env * HA_DR_SIZE : nullptr;
+}
+
+template <int FAM, int MODE>
+__device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, const ha_params_t* __restrict__ params,
+                                         const ha_state_t& st, int num_envs, int n_calls, uint32_t flags,
+                                         int stat_slot, float* __restrict__ spill,
+                                         const int32_t* __restrict__ env_ids, const StepIO& io) {
+    using F = Family<FAM>;
+    constexpr int TASK = F::task;
+    using PC = typename F::Phys;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // one workgroup per env; ha_simulate_envs launches one per listed env
+    int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
+    if (env < 0 || env >= num_envs) return;
+    SimCtx c;
+    // what this body sets its own way comes first, in the order it has always read params / model / st in (the
+    // kernels' instruction schedule follows that order); sim_ctx_init then fills in the shared fields
+    float* area = (PC::split || PC::ovf || PC::selfc) ? spill + (size_t)env * PC::spill_floats : nullptr;
+    c.selfc = PC::selfc ? reinterpret_cast<uint8_t*>(area + PC::off_selfc) : nullptr;
+    // separating-face records of the broad phase's pairs (Family pair_face_records: the clutter family only)
+    c.pairf = (area && F::pair_face_records) ? reinterpret_cast<uint8_t*>(area + PC::off_pairf) : nullptr;
+#ifdef HA_X_NO_PAIRF    /* A/B builds only: no separating-face records for the broad phase's pairs */
+    c.pairf = nullptr;
+#endif
+    // persistent contact manifolds (ha_params_t v13): the env's records, when the caller bound the buffer and the
+    // tolerance is on; slots = detect's pairs + the self pairs (ha_contact_cache_slots)
+    if constexpr (F::pcm) {
+        size_t slots = pair_slots(params->n_objects, model->n_static, model->n_link_hulls) + model->n_self_pairs;
+        c.pcm = (st.contact_cache && params->pcm_lin_tol > 0.0f) ? st.contact_cache + (size_t)env * slots * HA_PCM_REC
+                                                                   : nullptr;
+    } else {
+        c.pcm = nullptr;
+    }
+#ifdef HA_X_NO_PCM     /* A/B builds only: the persistent-manifold code compiled out */
+    c.pcm = nullptr;
+#endif
     c.act_in = MODE == MODE_STEP ? io.act_in : nullptr;
     c.obs_out = MODE == MODE_STEP ? io.obs_out : nullptr;
     c.clip_act = io.clip_act;
     c.clip_obs = io.clip_obs;
-    c.maxc = PC::cap * NCH;
-    // overflow chunks: contact entries past chunk 0 in the env's global area (null otherwise: ct_global folds away)
-    c.kg = PC::ovf ? reinterpret_cast<ContactLDS*>(c.spill + PC::off_ct) : nullptr;
-    c.kc0 = PC::ovf ? PC::cap : PC::cap * NCH;
-    c.lane = threadIdx.x;
-    c.D = ND;                     // == model->n_dofs (ha_create); a constant, so loops over D unroll
-    c.NO = params->n_objects;
-    c.L = model->n_links;
-    c.dr = (params->dr_enable && st.dr_scale) ? st.dr_scale + (size_t)env * HA_DR_SIZE : nullptr;
+    sim_ctx_init<PC>(c, model, params, st, env, smem, area);
     // v16: the shard-wide DR state (ha_dr_global_kernel ran before this launch); with it the per-env sampling, the
     // noise and the randomized gravity are on
     c.drg = (c.dr && st.dr_global) ? st.dr_global : nullptr;
@@ -733,7 +558,7 @@ __device__ unsigned int g_envhw[2 * 65536];
 #endif
 #define HA_KERNEL(name, FAM, MODE)                                                                              \
     extern "C" __global__ void __launch_bounds__(64)                                                          \
-        __attribute__((amdgpu_waves_per_eu(task_waves_per_eu<FAM>())))                                        \
+        __attribute__((amdgpu_waves_per_eu(Family<FAM>::waves_per_eu)))                                       \
         name(const ha_model_t* __restrict__ model, const ha_params_t* __restrict__ params, ha_state_t st,       \
              int num_envs, int n_calls, uint32_t flags, int stat_slot, float* spill, const int32_t* env_ids,     \
              StepIO io) {                                                                                       \
@@ -768,38 +593,6 @@ HA_KERNEL(ak_reset_kernel, HA_TASK_ALLEGRO_KUKA, MODE_RESET)
 
 typedef void (*env_kernel_t)(const ha_model_t*, const ha_params_t*, ha_state_t, int, int, uint32_t, int, float*,
                              const int32_t*, StepIO);
-static env_kernel_t kernel_for(int fam, int mode) {
-    if (fam == FAM_UR5SIH_CLUTTER) {
-        switch (mode) {
-            case MODE_STEP: return hb_step_kernel;
-            case MODE_SIMULATE: return hb_simulate_kernel;
-            case MODE_OBSERVE: return hb_observe_kernel;
-            default: return hb_reset_kernel;
-        }
-    }
-    if (fam == HA_TASK_ALLEGRO_KUKA) {
-        switch (mode) {
-            case MODE_STEP: return ak_step_kernel;
-            case MODE_SIMULATE: return ak_simulate_kernel;
-            case MODE_OBSERVE: return ak_observe_kernel;
-            default: return ak_reset_kernel;
-        }
-    }
-    if (fam == HA_TASK_ALLEGRO_HAND) {
-        switch (mode) {
-            case MODE_STEP: return ah_step_kernel;
-            case MODE_SIMULATE: return ah_simulate_kernel;
-            case MODE_OBSERVE: return ah_observe_kernel;
-            default: return ah_reset_kernel;
-        }
-    }
-    switch (mode) {
-        case MODE_STEP: return ha_step_kernel;
-        case MODE_SIMULATE: return ha_simulate_kernel;
-        case MODE_OBSERVE: return ha_observe_kernel;
-        default: return ha_reset_kernel;
-    }
-}
 
 // ----------------------------------------------------------------------------- contact query
 // ha_refresh_contacts: the contact list detect() produces for the bound state, as rows of HA_CONTACT_REC floats (layout
@@ -834,47 +627,22 @@ __device__ __forceinline__ void contacts_body(const ha_model_t* __restrict__ mod
                                               const ha_state_t& st, int num_envs, float* __restrict__ spill,
                                               const int32_t* __restrict__ env_ids, float* __restrict__ contacts,
                                               int32_t* __restrict__ counts, int max_contacts) {
-    constexpr int NCH = task_contact_chunks<FAM>();
     using PC = FamPhys<FAM>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int env = env_ids ? env_ids[blockIdx.x] : (int)blockIdx.x;
     if (env < 0 || env >= num_envs) return;
     SimCtx c;
-    c.gather = false;
-#ifdef HA_AB_TIMING
-    c.dry = false;
-#endif
-    c.m = model;
-    c.p = params;
-    c.s = reinterpret_cast<EnvLDS*>(smem);
-    c.Minv = reinterpret_cast<float*>(smem + minv_lds_offset<PC>());
-    c.col = col_view<PC>(&c.s->u);
-    c.o = reinterpret_cast<ObjLDS*>(smem + obj_lds_offset<PC>());
-    c.k = reinterpret_cast<ContactLDS*>(smem + contact_lds_offset<PC>());
-    c.spill = PC::ovf ? spill + (size_t)env * PC::spill_floats : nullptr;
+    // of the env's global area only the overflow chunks' contact entries; no record, no step I/O, no DR sampling
+    sim_ctx_init<PC>(c, model, params, st, env, smem, PC::ovf ? spill + (size_t)env * PC::spill_floats : nullptr);
     c.selfc = nullptr;
     c.pairf = nullptr;
-    c.selfm = PC::selfc ? reinterpret_cast<uint32_t*>(smem + selfm_lds_offset<PC>()) : nullptr;
-    c.sepf = 0xFF;
     c.pcm = nullptr;
-    c.pslot = -1;
-    c.pkind = c.pA = c.pB = 0;
-    c.pemit = 0;
 #ifdef HA_PROFILE
     c.pk = 0;
-    c.pcls = 0;
 #endif
     c.act_in = nullptr;
     c.obs_out = nullptr;
     c.clip_act = c.clip_obs = 0.0f;
-    c.maxc = PC::cap * NCH;
-    c.kg = PC::ovf ? reinterpret_cast<ContactLDS*>(c.spill + PC::off_ct) : nullptr;
-    c.kc0 = PC::ovf ? PC::cap : PC::cap * NCH;
-    c.lane = threadIdx.x;
-    c.D = task_nd<FAM>();
-    c.NO = params->n_objects;
-    c.L = model->n_links;
-    c.dr = (params->dr_enable && st.dr_scale) ? st.dr_scale + (size_t)env * HA_DR_SIZE : nullptr;
     c.drg = nullptr;
     c.rp = nullptr;
     c.last = false;
@@ -887,7 +655,7 @@ __device__ __forceinline__ void contacts_body(const ha_model_t* __restrict__ mod
     nc = nc < max_contacts ? nc : max_contacts;     // the host entry checks max_contacts >= the capacity
     float* out = contacts + (size_t)env * max_contacts * HA_CONTACT_REC;
     // lane i: contacts i and i + 64 (the capacity is at most 128); five 16-byte stores per 80-byte row
-    static_assert(PC::cap * NCH <= 128, "two contacts per lane");
+    static_assert(PC::cap * PC::nch <= 128, "two contacts per lane");
     for (int ci = c.lane; ci < nc; ci += 64) {
         ContactLDS k = ct_get(c, ci);
         f3 x = ld3(k.x), n = ld3(k.n);
@@ -920,13 +688,47 @@ HA_CONTACTS_KERNEL(ah_contacts_kernel, HA_TASK_ALLEGRO_HAND)
 HA_CONTACTS_KERNEL(ak_contacts_kernel, HA_TASK_ALLEGRO_KUKA)
 typedef void (*contacts_kernel_t)(const ha_model_t*, const ha_params_t*, ha_state_t, int, float*, const int32_t*, float*,
                                   int32_t*, int);
-static contacts_kernel_t contacts_kernel_for(int fam) {
-    switch (fam) {
-        case FAM_UR5SIH_CLUTTER: return hb_contacts_kernel;
-        case HA_TASK_ALLEGRO_HAND: return ah_contacts_kernel;
-        case HA_TASK_ALLEGRO_KUKA: return ak_contacts_kernel;
-        default: return ha_contacts_kernel;
-    }
+
+// ----------------------------------------------------------------------------- the host's view of a family
+// What the C ABI below needs of a kernel family at run time: Family<FAM>'s constants and the family's kernels. One
+// instance per family, filled from Family<FAM>; the handle keeps a pointer to its family's.
+struct FamilyInfo {
+    int nd, obj_capacity;
+    int contacts;               // contacts per substep (ha_contact_capacity)
+    int colv, colp, colg;       // narrow-phase scratch: largest hull (vertices, planes), gather points (0: none)
+    size_t col_bytes;
+    int pairf_bytes;            // pairs the separating-face records hold
+    int row_stride;
+    size_t lds_bytes;           // dynamic LDS of every launch of the family's kernels
+    size_t spill_floats;        // the env's global area
+    bool pcm, selfc;            // takes persistent-manifold records / self-collision pairs
+    env_kernel_t env_kernel[4]; // by MODE_*
+    contacts_kernel_t contacts_kernel;
+};
+template <int FAM>
+static FamilyInfo make_family_info(env_kernel_t simulate, env_kernel_t step, env_kernel_t observe, env_kernel_t reset,
+                                   contacts_kernel_t contacts) {
+    using F = Family<FAM>;
+    using PC = typename F::Phys;
+    static_assert(MODE_SIMULATE == 0 && MODE_STEP == 1 && MODE_OBSERVE == 2 && MODE_RESET == 3, "env_kernel order");
+    return FamilyInfo{F::nd, F::obj_capacity, PC::cap * PC::nch, PC::colv, PC::colp, PC::colg, PC::col_bytes,
+                      PC::pairf_bytes, row_stride<F::nd>(), task_lds_bytes<PC>(), (size_t)PC::spill_floats, F::pcm,
+                      F::selfc, {simulate, step, observe, reset}, contacts};
+}
+static const FamilyInfo& family_info(int fam) {
+    static_assert(HA_TASK_UR5SIH == 0 && HA_TASK_ALLEGRO_HAND == 1 && HA_TASK_ALLEGRO_KUKA == 2 &&
+                      FAM_UR5SIH_CLUTTER == 3, "the table is indexed by the family id");
+    static const FamilyInfo info[4] = {
+        make_family_info<HA_TASK_UR5SIH>(ha_simulate_kernel, ha_step_kernel, ha_observe_kernel, ha_reset_kernel,
+                                         ha_contacts_kernel),
+        make_family_info<HA_TASK_ALLEGRO_HAND>(ah_simulate_kernel, ah_step_kernel, ah_observe_kernel, ah_reset_kernel,
+                                               ah_contacts_kernel),
+        make_family_info<HA_TASK_ALLEGRO_KUKA>(ak_simulate_kernel, ak_step_kernel, ak_observe_kernel, ak_reset_kernel,
+                                               ak_contacts_kernel),
+        make_family_info<FAM_UR5SIH_CLUTTER>(hb_simulate_kernel, hb_step_kernel, hb_observe_kernel, hb_reset_kernel,
+                                             hb_contacts_kernel),
+    };
+    return info[fam];
 }
 
 // ----------------------------------------------------------------------------- indexed setters
@@ -1022,6 +824,7 @@ struct ha_handle_s {
     ha_params_t* d_params;
     ha_params_t h_params;
     int N, NO, D, L, A, B, task, fam;
+    const FamilyInfo* fi; // the family's constants and kernels (family_info(fam))
     int a0;               // actor_object0 (host copy)
     int pcm_slots;        // persistent-manifold record slots per env (ha_contact_cache_slots)
     ha_state_t st;
@@ -1058,59 +861,10 @@ struct ha_handle_s {
         }                                                                             \
     } while (0)
 
-// per-family shape (object capacity, LDS bytes, row stride), from the same templates the kernels use
-template <int FAM>
-static size_t fam_lds_bytes() { return task_lds_bytes<FamPhys<FAM>>(); }
-static size_t spill_floats(int fam) {
-    switch (fam) {
-        case FAM_UR5SIH_CLUTTER: return FamPhys<FAM_UR5SIH_CLUTTER>::spill_floats;
-        case HA_TASK_ALLEGRO_HAND: return FamPhys<HA_TASK_ALLEGRO_HAND>::spill_floats;
-        case HA_TASK_ALLEGRO_KUKA: return FamPhys<HA_TASK_ALLEGRO_KUKA>::spill_floats;
-        default: return FamPhys<HA_TASK_UR5SIH>::spill_floats;
-    }
-}
-static int pairf_bytes(int fam) {
-    switch (fam) {
-        case FAM_UR5SIH_CLUTTER: return FamPhys<FAM_UR5SIH_CLUTTER>::pairf_bytes;
-        case HA_TASK_ALLEGRO_HAND: return FamPhys<HA_TASK_ALLEGRO_HAND>::pairf_bytes;
-        case HA_TASK_ALLEGRO_KUKA: return FamPhys<HA_TASK_ALLEGRO_KUKA>::pairf_bytes;
-        default: return FamPhys<HA_TASK_UR5SIH>::pairf_bytes;
-    }
-}
-static int obj_capacity(int fam) {
-    switch (fam) {
-        case FAM_UR5SIH_CLUTTER: return task_obj_capacity<FAM_UR5SIH_CLUTTER>();
-        case HA_TASK_ALLEGRO_HAND: return task_obj_capacity<HA_TASK_ALLEGRO_HAND>();
-        case HA_TASK_ALLEGRO_KUKA: return task_obj_capacity<HA_TASK_ALLEGRO_KUKA>();
-        default: return task_obj_capacity<HA_TASK_UR5SIH>();
-    }
-}
-static size_t lds_bytes(int fam) {
-    switch (fam) {
-        case FAM_UR5SIH_CLUTTER: return fam_lds_bytes<FAM_UR5SIH_CLUTTER>();
-        case HA_TASK_ALLEGRO_HAND: return fam_lds_bytes<HA_TASK_ALLEGRO_HAND>();
-        case HA_TASK_ALLEGRO_KUKA: return fam_lds_bytes<HA_TASK_ALLEGRO_KUKA>();
-        default: return fam_lds_bytes<HA_TASK_UR5SIH>();
-    }
-}
-template <int FAM>
-static int fam_contacts() { return FamPhys<FAM>::cap * FamPhys<FAM>::nch; }
-static int contact_capacity(int fam) {
-    switch (fam) {
-        case FAM_UR5SIH_CLUTTER: return fam_contacts<FAM_UR5SIH_CLUTTER>();
-        case HA_TASK_ALLEGRO_HAND: return fam_contacts<HA_TASK_ALLEGRO_HAND>();
-        case HA_TASK_ALLEGRO_KUKA: return fam_contacts<HA_TASK_ALLEGRO_KUKA>();
-        default: return fam_contacts<HA_TASK_UR5SIH>();
-    }
-}
-static int task_row_stride(int task) {
-    return task == HA_TASK_ALLEGRO_KUKA ? row_stride<AK_ND>()
-                                        : (task == HA_TASK_ALLEGRO_HAND ? row_stride<AH_ND>() : row_stride<HA_ND>());
-}
 // kernel family of a task configuration: Ur5Sih with more objects than the dense family's 3 slots runs the
 // clutter family (bin-picking)
 static int family_of(const ha_params_t* p) {
-    if (p->task == HA_TASK_UR5SIH && p->n_objects > task_obj_capacity<HA_TASK_UR5SIH>()) return FAM_UR5SIH_CLUTTER;
+    if (p->task == HA_TASK_UR5SIH && p->n_objects > Family<HA_TASK_UR5SIH>::obj_capacity) return FAM_UR5SIH_CLUTTER;
     return p->task;
 }
 
@@ -1144,13 +898,43 @@ static bool hull_in_box(const ha_model_t* m, int k) {
     return true;
 }
 
+// ha_create's device side: the model and params copies, the family's global area, its kernels' LDS size, the events.
+// On a failure the caller destroys the handle with whatever this got as far as allocating
+static int create_device_state(ha_handle h, const ha_model_t* model, const ha_params_t* params) {
+    const FamilyInfo& fi = *h->fi;
+    HIPCHK(hipMalloc(&h->d_model, sizeof(ha_model_t)));
+    HIPCHK(hipMalloc(&h->d_params, sizeof(ha_params_t)));
+    HIPCHK(hipMemcpy(h->d_model, model, sizeof(ha_model_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_params, params, sizeof(ha_params_t), hipMemcpyHostToDevice));
+    if (fi.spill_floats) {
+        HIPCHK(hipMalloc(&h->d_spill, sizeof(float) * fi.spill_floats * (size_t)h->N));
+        // every byte 0xFF: the self-collision records start as "no separating face" (the other areas are written
+        // before they are read)
+        HIPCHK(hipMemset(h->d_spill, 0xFF, sizeof(float) * fi.spill_floats * (size_t)h->N));
+    }
+    if (h->fam == HA_TASK_ALLEGRO_KUKA) {
+        size_t G = ((size_t)h->N + 63) / 64;
+        HIPCHK(hipMalloc(&h->d_io_partials, sizeof(float) * 4 * G));
+        HIPCHK(hipMalloc(&h->d_io_counters, sizeof(int32_t) * (G + 1)));
+        HIPCHK(hipMemset(h->d_io_counters, 0, sizeof(int32_t) * (G + 1)));
+    }
+    for (env_kernel_t k : fi.env_kernel)
+        HIPCHK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fi.lds_bytes));
+    HIPCHK(hipFuncSetAttribute((const void*)fi.contacts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)fi.lds_bytes));
+    HIPCHK(hipEventCreate(&h->ev0));
+    HIPCHK(hipEventCreate(&h->ev1));
+    return HA_OK;
+}
+
 int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_envs, ha_handle* out) {
     if (!model || !params || !out || num_envs <= 0) return HA_E_ARG;
     if (params->task != HA_TASK_UR5SIH && params->task != HA_TASK_ALLEGRO_HAND && params->task != HA_TASK_ALLEGRO_KUKA)
         return HA_E_ARG;
+    int fam = family_of(params);
+    const FamilyInfo& fi = family_info(fam);
     // the kernels are compiled for the task's DOF count (register-resident factorization)
-    int nd = params->task == HA_TASK_ALLEGRO_HAND ? AH_ND : (params->task == HA_TASK_ALLEGRO_KUKA ? AK_ND : HA_ND);
-    if (model->n_dofs != nd) return HA_E_MODEL;
+    if (model->n_dofs != fi.nd) return HA_E_MODEL;
     if (params->task == HA_TASK_ALLEGRO_KUKA) {
         if (params->n_objects != 1 || params->ak_num_keypoints < 1 || params->ak_num_keypoints > 4 ||
             params->num_obs > AK_MAX_OBS || params->num_obs != 93 + 6 * params->ak_num_keypoints)
@@ -1175,7 +959,6 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
         }
     }
     if (model->n_actors < 1 || model->n_bodies < model->n_links + params->n_objects) return HA_E_MODEL;
-    int fam = family_of(params);
     if (params->task == HA_TASK_UR5SIH && params->num_obs != 108 + 13 * params->n_objects) return HA_E_ARG;
     // AllegroHand observation types (v15): num_obs is the type's size (allegro_hand.py:106-112)
     if (params->task == HA_TASK_ALLEGRO_HAND &&
@@ -1188,8 +971,8 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
     if (model->n_fixed_bodies < 0 || model->n_fixed_bodies > HA_MAX_FIXED_BODIES ||
         (model->n_fixed_bodies > 0 && (model->body_fixed0 < 0 || model->body_fixed0 + model->n_fixed_bodies > model->n_bodies)))
         return HA_E_MODEL;
-    if (model->n_links > HA_MAX_LINKS || params->n_objects < 1 || params->n_objects > obj_capacity(fam) ||
-        model->n_dofs + 6 * (params->n_objects < 2 ? params->n_objects : 2) > task_row_stride(params->task) ||
+    if (model->n_links > HA_MAX_LINKS || params->n_objects < 1 || params->n_objects > fi.obj_capacity ||
+        model->n_dofs + 6 * (params->n_objects < 2 ? params->n_objects : 2) > fi.row_stride ||
         model->n_dofs + 6 * params->n_objects > MAXV || model->n_bodies > MAXB ||
         model->n_static < 0 || model->n_static > HA_MAX_STATIC || model->n_pool < 1 || model->n_pool > HA_MAX_POOL ||
         model->n_hulls > HA_MAX_HULLS)
@@ -1201,21 +984,12 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
     if (params->task == HA_TASK_ALLEGRO_KUKA && params->ak_subtask == 2 && model->posed_actor != model->actor_goal)
         return HA_E_MODEL;
     // every hull must fit the family's narrow-phase scratch (ColLayout)
-    int col_v = (fam == HA_TASK_ALLEGRO_KUKA || fam == HA_TASK_ALLEGRO_HAND) ? FamPhys<HA_TASK_ALLEGRO_HAND>::colv
-                                                                           : FamPhys<HA_TASK_UR5SIH>::colv;
-    int col_p = (fam == HA_TASK_ALLEGRO_KUKA || fam == HA_TASK_ALLEGRO_HAND) ? FamPhys<HA_TASK_ALLEGRO_HAND>::colp
-                                                                           : FamPhys<HA_TASK_UR5SIH>::colp;
-    static_assert(FamPhys<HA_TASK_ALLEGRO_HAND>::colv == FamPhys<HA_TASK_ALLEGRO_KUKA>::colv &&
-                      FamPhys<HA_TASK_ALLEGRO_HAND>::colp == FamPhys<HA_TASK_ALLEGRO_KUKA>::colp &&
-                      FamPhys<HA_TASK_UR5SIH>::colv == FamPhys<FAM_UR5SIH_CLUTTER>::colv &&
-                      FamPhys<HA_TASK_UR5SIH>::colp == FamPhys<FAM_UR5SIH_CLUTTER>::colp,
-                  "narrow-phase scratch limits per family pair");
     for (int k = 0; k < model->n_hulls; k++) {
-        if (model->hull_nverts[k] > col_v || model->hull_nplanes[k] > col_p) return HA_E_MODEL;
+        if (model->hull_nverts[k] > fi.colv || model->hull_nplanes[k] > fi.colp) return HA_E_MODEL;
         // v10 topology: the edge-edge SAT keeps a hull's culled edge list as bytes in the scratch's candidate arrays
-        // (4 x col_v bytes each); a clipped manifold's candidates take 2 lanes per incident loop edge and one per
+        // (4 x colv bytes each); a clipped manifold's candidates take 2 lanes per incident loop edge and one per
         // reference loop vertex (FaceCands), so loops hold <= HA_MAX_FACE_LOOP vertices
-        if (model->hull_nedges[k] < 0 || model->hull_nedges[k] > 4 * col_v || model->hull_nplanes[k] > 256 ||
+        if (model->hull_nedges[k] < 0 || model->hull_nedges[k] > 4 * fi.colv || model->hull_nplanes[k] > 256 ||
             model->hull_edge_start[k] < 0 || model->hull_edge_start[k] + model->hull_nedges[k] > HA_MAX_EDGES)
             return HA_E_MODEL;
         // the topology records index the hull's LDS vertex / plane scratch directly: every index must be in range
@@ -1255,25 +1029,27 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
     }
     // self-collision pairs (v12): two link hulls of the model each; only the Allegro families' kernels run them
     if (model->n_self_pairs < 0 || model->n_self_pairs > HA_MAX_SELF_PAIRS) return HA_E_MODEL;
-    if (model->n_self_pairs > 0 && params->task == HA_TASK_UR5SIH) return HA_E_MODEL;
+    if (model->n_self_pairs > 0 && !fi.selfc) return HA_E_MODEL;
     // the self-pair pass keeps a 64-byte world box per link hull, a 2-byte entry per pair and 64 candidate entries in
     // the narrow-phase scratch (detect_self)
     if (model->n_self_pairs > 0 &&
-        (size_t)model->n_link_hulls * 64 + 2 * (size_t)model->n_self_pairs + 128 > (fam == HA_TASK_ALLEGRO_HAND ? FamPhys<HA_TASK_ALLEGRO_HAND>::col_bytes
-                                                                        : FamPhys<HA_TASK_ALLEGRO_KUKA>::col_bytes))
+        (size_t)model->n_link_hulls * 64 + 2 * (size_t)model->n_self_pairs + 128 > fi.col_bytes)
         return HA_E_MODEL;
     for (int k = 0; k < model->n_self_pairs; k++) {
         int a = model->self_pair[k] & 255, b = model->self_pair[k] >> 8;
         if (a >= model->n_link_hulls || b >= model->n_link_hulls || a == b) return HA_E_MODEL;
     }
     // a family without a gather buffer (ColLayout NG = 0) takes single-hull pool objects only
-    bool one_hull = (fam == HA_TASK_ALLEGRO_KUKA && FamPhys<HA_TASK_ALLEGRO_KUKA>::colg == 0) ||
-                    (fam == HA_TASK_ALLEGRO_HAND && FamPhys<HA_TASK_ALLEGRO_HAND>::colg == 0);
     for (int i = 0; i < model->n_pool; i++)
         if (model->pool_nhull[i] < 1 || model->pool_hull[i] < 0 ||
-            model->pool_hull[i] + model->pool_nhull[i] > model->n_hulls || (one_hull && model->pool_nhull[i] != 1))
+            model->pool_hull[i] + model->pool_nhull[i] > model->n_hulls || (fi.colg == 0 && model->pool_nhull[i] != 1))
             return HA_E_MODEL;
     if (params->num_initial_poses < 1 || params->num_initial_poses > HA_MAX_INIT_POSES) return HA_E_ARG;
+    // the broad phase's pairs must fit the family's separating-face records (one byte each in the env's global area)
+    const size_t pairs = pair_slots(params->n_objects, model->n_static, model->n_link_hulls);
+    if (pairs > (size_t)fi.pairf_bytes) return HA_E_MODEL;
+    // persistent-manifold records (v13): none when the tolerance is off, and none in a family built without them
+    if (params->pcm_lin_tol > 0.0f && !fi.pcm) return HA_E_ARG;
     ha_handle h = (ha_handle)calloc(1, sizeof(ha_handle_s));
     h->N = num_envs;
     h->NO = params->n_objects;
@@ -1284,6 +1060,7 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
     h->a0 = model->actor_object0;
     h->task = params->task;
     h->fam = fam;
+    h->fi = &fi;
     h->h_params = *params;
     h->stat_slots = 1;
     // links come after their parents (the FK's levels rely on it too), so one pass fills the per-link chains
@@ -1294,40 +1071,13 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
         h->link_path[i] = (child ? h->link_path[par] : 0u) | (1u << i);
         h->link_depth[i] = model->link_level[i];
     }
-    // the broad phase's pairs must fit the family's separating-face records (one byte each in the env's global area)
-    {
-        int NO = params->n_objects, NS = model->n_static, NLH = model->n_link_hulls;
-        if (NO * (1 + NS + NLH) + NO * (NO - 1) / 2 + NLH * NS > pairf_bytes(fam)) return HA_E_MODEL;
+    h->pcm_slots = params->pcm_lin_tol <= 0.0f ? 0 : (int)pairs + model->n_self_pairs;
+    // from here on a failure leaves a partly built handle: ha_destroy releases whatever it holds
+    int rc = create_device_state(h, model, params);
+    if (rc != HA_OK) {
+        ha_destroy(h);
+        return rc;
     }
-    // persistent-manifold records (v13): none when the tolerance is off, and none in a family built without them
-    if (params->pcm_lin_tol > 0.0f && !family_pcm(fam)) return HA_E_ARG;
-    h->pcm_slots = params->pcm_lin_tol <= 0.0f ? 0 :
-                   params->n_objects * (1 + model->n_static + model->n_link_hulls) +
-                   params->n_objects * (params->n_objects - 1) / 2 + model->n_link_hulls * model->n_static +
-                   model->n_self_pairs;
-    HIPCHK(hipMalloc(&h->d_model, sizeof(ha_model_t)));
-    HIPCHK(hipMalloc(&h->d_params, sizeof(ha_params_t)));
-    HIPCHK(hipMemcpy(h->d_model, model, sizeof(ha_model_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_params, params, sizeof(ha_params_t), hipMemcpyHostToDevice));
-    if (spill_floats(fam)) {
-        HIPCHK(hipMalloc(&h->d_spill, sizeof(float) * spill_floats(fam) * (size_t)num_envs));
-        // every byte 0xFF: the self-collision records start as "no separating face" (the other areas are written
-        // before they are read)
-        HIPCHK(hipMemset(h->d_spill, 0xFF, sizeof(float) * spill_floats(fam) * (size_t)num_envs));
-    }
-    if (fam == HA_TASK_ALLEGRO_KUKA) {
-        size_t G = ((size_t)num_envs + 63) / 64;
-        HIPCHK(hipMalloc(&h->d_io_partials, sizeof(float) * 4 * G));
-        HIPCHK(hipMalloc(&h->d_io_counters, sizeof(int32_t) * (G + 1)));
-        HIPCHK(hipMemset(h->d_io_counters, 0, sizeof(int32_t) * (G + 1)));
-    }
-    for (int mode : {MODE_STEP, MODE_SIMULATE, MODE_OBSERVE, MODE_RESET})
-        HIPCHK(hipFuncSetAttribute((const void*)kernel_for(h->fam, mode), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds_bytes(h->fam)));
-    HIPCHK(hipFuncSetAttribute((const void*)contacts_kernel_for(h->fam), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds_bytes(h->fam)));
-    HIPCHK(hipEventCreate(&h->ev0));
-    HIPCHK(hipEventCreate(&h->ev1));
     *out = h;
     return HA_OK;
 }
@@ -1342,8 +1092,8 @@ int ha_destroy(ha_handle h) {
     if (h->d_tstart) (void)hipFree(h->d_tstart);
     if (h->d_tend) (void)hipFree(h->d_tend);
     if (h->d_drr) (void)hipFree(h->d_drr);
-    (void)hipEventDestroy(h->ev0);
-    (void)hipEventDestroy(h->ev1);
+    if (h->ev0) (void)hipEventDestroy(h->ev0);      // null: ha_create failed before it made them
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
     free(h);
     return HA_OK;
 }
@@ -1397,7 +1147,7 @@ static int launch(ha_handle h, int mode, int n_calls, uint32_t flags, int slot, 
         env_ids = h->order;
         n_ids = h->N;
     }
-    hipLaunchKernelGGL(kernel_for(h->fam, mode), dim3(env_ids ? n_ids : h->N), dim3(64), lds_bytes(h->fam), s, h->d_model,
+    hipLaunchKernelGGL(h->fi->env_kernel[mode], dim3(env_ids ? n_ids : h->N), dim3(64), h->fi->lds_bytes, s, h->d_model,
                        h->d_params, h->st, h->N, n_calls, flags, slot, h->d_spill, env_ids, io);
     HIPCHK(hipGetLastError());
     if (rec) {
@@ -1812,10 +1562,10 @@ int ha_refresh_kinematics(ha_handle h, const ha_kinematics_t* k, void* stream) {
 int ha_refresh_contacts(ha_handle h, const ha_contacts_t* c, void* stream) {
     if (!h || !c) return HA_E_ARG;
     if (!c->contacts || !c->counts || ((uintptr_t)c->contacts & 15)) return HA_E_ARG;
-    if (c->max_contacts < contact_capacity(h->fam)) return HA_E_ARG;
+    if (c->max_contacts < h->fi->contacts) return HA_E_ARG;
     if (c->env_ids && (c->n_envs < 1 || c->n_envs > h->N)) return HA_E_ARG;
     if (!h->bound) return HA_E_STATE;
-    hipLaunchKernelGGL(contacts_kernel_for(h->fam), dim3(c->env_ids ? c->n_envs : h->N), dim3(64), lds_bytes(h->fam),
+    hipLaunchKernelGGL(h->fi->contacts_kernel, dim3(c->env_ids ? c->n_envs : h->N), dim3(64), h->fi->lds_bytes,
                        (hipStream_t)stream, h->d_model, h->d_params, h->st, h->N, h->d_spill, c->env_ids, c->contacts,
                        c->counts, c->max_contacts);
     HIPCHK(hipGetLastError());
@@ -1964,7 +1714,7 @@ int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv,
     return HA_OK;
 }
 
-int ha_contact_capacity(ha_handle h) { return h ? contact_capacity(h->fam) : HA_E_ARG; }
+int ha_contact_capacity(ha_handle h) { return h ? h->fi->contacts : HA_E_ARG; }
 
 float ha_last_kernel_ms(ha_handle h) {
     if (!h || !h->timed || !h->t_ev || h->t_count < 1) return -1.0f;
