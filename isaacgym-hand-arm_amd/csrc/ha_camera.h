@@ -16,8 +16,7 @@
 // the hull in its own frame (local planes read from the model, L1/L2-resident).
 #pragma once
 #include "ha_task.h"
-
-#define HA_CAM_MAX_HULLS (HA_MAX_HULLS + 1)
+#include "ha_cam_hulls.h"   /* HA_CAM_MAX_HULLS and the host's worst-case count of hl[] entries */
 
 struct CamLaunch {
     ha_camera_t cam;
@@ -120,11 +119,15 @@ extern "C" __global__ void __launch_bounds__(256) ha_camera_kernel(CamLaunch L) 
         }
         {                                                              // goal sphere (visual only, multi_object.py:581)
             const float* g = L.goal_pos + (size_t)env * 3;
+            // through the closest approach to the centre: the half chord r^2 - |off|^2 is formed from small terms (the
+            // discriminant b^2 - dd c cancels two terms of the size of the camera distance squared, and lost the
+            // depth of a 2 cm sphere at 0.5 m to 1e-6)
             const f3 oc = o - mk3(g[0], g[1], g[2]);
-            const float b = dot3(oc, d), c = dot3(oc, oc) - cam.goal_radius * cam.goal_radius;
-            const float disc = b * b - dd * c;
-            if (disc >= 0.0f) {
-                const float t = (-b - sqrtf(disc)) / dd;
+            const float tc = -dot3(oc, d) / dd;
+            const f3 off = oc + d * tc;
+            const float h2 = cam.goal_radius * cam.goal_radius - dot3(off, off);
+            if (h2 >= 0.0f) {
+                const float t = tc - sqrtf(h2 / dd);
                 if (t > 0.0f && t < best) { best = t; bseg = 3 + L.NO; }
             }
         }

@@ -850,6 +850,8 @@ struct ha_handle_s {
     // ha_cartesian_targets: per link its ancestor-or-self DOFs, the links from the base to it, and its depth
     uint32_t link_dofs[HA_MAX_LINKS], link_path[HA_MAX_LINKS];
     int link_depth[HA_MAX_LINKS];
+    // ha_render_camera: the model fields its launch needs and the worst-case hull-table size (ha_cam_hull_count)
+    int cam_link_hulls, cam_static, cam_body_robot0, cam_hulls;
 };
 
 #define HIPCHK(x)                                                                     \
@@ -1063,6 +1065,11 @@ int ha_create(const ha_model_t* model, const ha_params_t* params, int32_t num_en
     h->fi = &fi;
     h->h_params = *params;
     h->stat_slots = 1;
+    h->cam_link_hulls = model->n_link_hulls;
+    h->cam_static = model->n_static;
+    h->cam_body_robot0 = model->body_robot0;
+    h->cam_hulls = ha_cam_hull_count(model->n_link_hulls, model->n_static, model->n_pool, model->pool_nhull,
+                                     params->n_objects);
     // links come after their parents (the FK's levels rely on it too), so one pass fills the per-link chains
     for (int i = 0; i < model->n_links; i++) {
         int par = model->link_parent[i], d = model->link_dof[i];
@@ -1644,20 +1651,8 @@ int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv,
         return HA_E_ARG;
     if ((flags & HA_CAM_FROM_DEPTH) && (!cam->depth || !cam->pointcloud)) return HA_E_ARG;
     if (h->NO > HA_MAX_OBJ) return HA_E_ARG;
-    ha_model_t hm;      // the host copy of the few model fields the launch needs
-    HIPCHK(hipMemcpy(&hm.n_link_hulls, &h->d_model->n_link_hulls, sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&hm.n_static, &h->d_model->n_static, sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&hm.body_robot0, &h->d_model->body_robot0, sizeof(int32_t), hipMemcpyDeviceToHost));
-    // the most pieces any env's objects can have: the NO largest pool_nhull
-    int nh[HA_MAX_POOL], pieces = 0;
-    for (int i = 0; i < hm.n_pool && i < HA_MAX_POOL; i++) nh[i] = hm.pool_nhull[i];
-    for (int o = 0; o < h->NO; o++) {
-        int bi = -1;
-        for (int i = 0; i < hm.n_pool && i < HA_MAX_POOL; i++)
-            if (nh[i] > 0 && (bi < 0 || nh[i] > nh[bi])) bi = i;
-        if (bi >= 0) { pieces += nh[bi]; nh[bi] = 0; }
-    }
-    if (hm.n_link_hulls + pieces + hm.n_static > HA_CAM_MAX_HULLS || hm.n_link_hulls > 256) return HA_E_MODEL;
+    // the worst-case hull table of an env (ha_cam_hull_count, from the host model at ha_create) must fit the kernel's
+    if (h->cam_hulls < 0 || h->cam_hulls > HA_CAM_MAX_HULLS || h->cam_link_hulls > 256) return HA_E_MODEL;
     CamLaunch L;
     L.cam = *cam;
     L.m = h->d_model;
@@ -1670,9 +1665,9 @@ int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv,
     L.B = h->B;
     L.a0 = h->a0;
     L.NO = h->NO;
-    L.body_robot0 = hm.body_robot0;
-    L.n_link_hulls = hm.n_link_hulls;
-    L.n_static = hm.n_static;
+    L.body_robot0 = h->cam_body_robot0;
+    L.n_link_hulls = h->cam_link_hulls;
+    L.n_static = h->cam_static;
     // camera frame (Isaac Gym: +X forward, +Y left, +Z up) -> view axes (x right = -Y, y up = Z, z back = -X)
     const float* q = cam->quat;
     float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);

@@ -398,6 +398,19 @@ def _topology(h):
 NO_TABLE_CONTACT = {"shoulder_link", "upper_arm_link"}
 
 
+def _f32_radius(center, radius, v32):
+    """The record's bounding-sphere radius as the model's float32: rounded up until the sphere about the float32 centre
+    holds every float32 vertex. The record's float64 sphere holds its float64 vertices, but rounding the centre, the
+    vertices and the radius to nearest left a vertex up to 2 ulps of the radius outside on 5 of the scene's 111 hulls,
+    and a ray grazing that vertex would be pruned by the camera's sphere test (csrc/ha_camera.h)."""
+    c = np.asarray(center, np.float32).astype(np.float64)
+    far = float(np.linalg.norm(v32.astype(np.float64) - c, axis=1).max())
+    r = np.float32(radius)
+    while float(r) < far:
+        r = np.nextafter(r, np.float32(np.inf))
+    return float(r)
+
+
 def build_model(scene, pool_names=None, posed=None):
     """posed: name of a group in scene["posed_statics"] (the AllegroKuka throw "bucket") whose convex pieces become
     statics carried by a per-env actor (ha_model_t v14 posed_actor / static_posed)."""
@@ -453,7 +466,7 @@ def build_model(scene, pool_names=None, posed=None):
         m.hull_vert_start[k], m.hull_nverts[k] = vs, len(v)
         m.hull_plane_start[k], m.hull_nplanes[k] = ps, len(p)
         m.hull_center[k][:] = h["center"]
-        m.hull_radius[k] = h["radius"]
+        m.hull_radius[k] = _f32_radius(h["center"], h["radius"], v)
         verts[vs:vs + len(v), :3] = v
         planes[ps:ps + len(p)] = p
         # v10 topology: edges (v0, v1, f0, f1) and per-plane face loops

@@ -3,7 +3,8 @@
 Only ``tests/`` may import this module, as the checker. It restates, in float32 and in the kernel's operation
 order:
   * the ray cast of depth / segmentation against the collision geometry (the build's stand-in for Isaac Gym's
-    closed renderer: parity against that renderer is unpinned, DESIGN.md §3.10);
+    closed renderer: parity against that renderer is unpinned); this restatement and the kernel are
+    both held to the float64 ray caster of tests/camera_ref.py, which shares nothing with either;
   * ``depth_image_to_global_points`` + ``_compute_pointcloud`` (hand_arm/utils/camera.py:50-69, 302-311), whose
     reference arithmetic is pinned by tests/golden/camera_pointcloud.npz (made by running the reference code).
 """
@@ -74,11 +75,11 @@ def render_depth_segmentation(m, cam, root, body, object_indices, goal_pos, a0, 
     hitg = ground & (tg > 0)
     best = np.where(hitg, tg, best)
     oc = o - np.asarray(goal_pos, F)
-    b = (oc * d).sum(-1, dtype=F)
-    c = F((oc * oc).sum(dtype=F) - F(cam["goal_radius"]) * F(cam["goal_radius"]))
-    disc = b * b - dd * c
-    tgoal = ((-b - np.sqrt(np.maximum(disc, 0))) / dd).astype(F)
-    hit = (disc >= 0) & (tgoal > 0) & (tgoal < best)
+    tcg = (-(oc * d).sum(-1, dtype=F) / dd).astype(F)          # closest approach to the centre
+    offg = oc + d * tcg[:, None]
+    h2 = F(cam["goal_radius"]) * F(cam["goal_radius"]) - (offg * offg).sum(-1, dtype=F)
+    tgoal = (tcg - np.sqrt(np.maximum(h2, 0) / dd)).astype(F)
+    hit = (h2 >= 0) & (tgoal > 0) & (tgoal < best)
     best = np.where(hit, tgoal, best)
     seg = np.where(hit, 3 + n_obj, seg)
     planes = np.array(m.planes, F)

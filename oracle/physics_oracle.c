@@ -31,6 +31,7 @@
 #include "../include/handarm_abi.h"
 #include "../include/ha_fmath.h"
 #include "../include/ha_obb.h"
+#include "../include/ha_cam_hulls.h"
 
 #define MAXC HA_MAX_CONTACTS   /* contact list capacity; a handle uses 21 (<= 3 objects) or 84 (clutter) */
 #define MAXR (3 * MAXC)
@@ -1574,3 +1575,9 @@ void hao_logexp(const float* x, int n, float* lo, float* ex) {
         ex[i] = ha_expf(x[i] * 1e-3f - 3.0f);
     }
 }
+/* test helper: the camera ray cast's worst-case hull-table size (include/ha_cam_hulls.h, the text ha_create compiles)
+   from bare counts, and the table's capacity */
+int hao_cam_hull_count(int n_link_hulls, int n_static, int n_pool, const int32_t* pool_nhull, int n_obj) {
+    return ha_cam_hull_count(n_link_hulls, n_static, n_pool, pool_nhull, n_obj);
+}
+int hao_cam_max_hulls(void) { return HA_CAM_MAX_HULLS; }
