@@ -194,6 +194,13 @@ struct Family {
     // register cost spills (tools/phase_profile.py, r5l)
     static constexpr bool pair_face_records = pick(false, true, false, false);
 
+    // the rows phase's diagonal term J_r . Y_r from Y_r read back in one batch after the loop over the DOFs (ha_solve.h
+    // substep YBATCH) instead of one reload of J_r[i] per DOF behind each store of Y_r[i]. Not AllegroHand: at 4 waves
+    // per SIMD (128 VGPRs) the second 22-float array costs its kernels scratch (ah_step_kernel 100 -> 120 B/lane,
+    // ah_simulate_kernel 92 -> 104; tools/res_usage.sh). Not the clutter family: no resource moves, but C5 measured
+    // 0.4% slower with it and level without (profiles/r10_rows_round_trips.txt). Both keep the reload
+    static constexpr bool rows_y_batch = pick(true, false, false, true);
+
     // the physics' compile-time shape (ha_physics.h). The compact layout: split rows, no gather buffer, S in the union
     using Phys = PhysCfg<nd, obj_capacity, contact_chunks, link_slots, lds_chunks, chunk_capacity, col_verts, col_planes,
                          compact ? 1 : -1, compact ? 0 : HA_MAX_GATHER, compact, recompute, overflow, self_pass,

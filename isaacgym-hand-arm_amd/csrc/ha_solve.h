@@ -83,7 +83,10 @@ HD void obj_entry(const SimCtx& c, int o, int a, f3 x, f3 dir, int t, float& j, 
 
 // SETS3: the PGS contact loop with its row entries in three register sets that rotate by name (below); a kernel that
 // would pay for them in scratch passes false and keeps the copy loop
-template <class PC, bool SETS3 = true>
+// YBATCH: the rows phase reads Y_r back in one batch for the diagonal term (below); a kernel that would pay for the
+// second register array in scratch, or runs slower with it, passes false and keeps the reload of J_r[i] inside the loop
+// (Family rows_y_batch)
+template <class PC, bool SETS3 = true, bool YBATCH = true>
 HD void substep(SimCtx& c, float hdt) {
     constexpr int ND = PC::nd, NCH = PC::nch, VW = PC::vw;
     constexpr int RSN = row_stride<ND>();
@@ -372,20 +375,48 @@ HD void substep(SimCtx& c, float hdt) {
 #pragma unroll
                     for (int j = 0; j < ND; j++) jr[j] = JrG[j];
                 }
+                constexpr bool YB = YBATCH;
+                // the rolled loop stores Y_r[i]. YB: nothing else, and the diagonal terms follow as one chain (i ascending,
+                // the dense row's order) over jr and Y_r read back in one batch, both statically indexed, in registers
+                // (D = ND): one round trip per row. Otherwise J_r[i] comes from the row again behind each store (the
+                // same value), one round trip per DOF
                 for (int i = 0; i < D; i++) {
                     float acc = 0.0f;
+                    // row i of M^-1 in one batch ahead of the chain (the fence keeps the loads together): left alone the
+                    // compiler loads it four entries at a time with a full LDS wait after each load, six round trips per
+                    // DOF
+                    float mr[ND];
 #pragma unroll
-                    for (int j = 0; j < ND; j++) acc = fmaf(c.Minv[i * D + j], jr[j], acc);
-                    // J_r[i] from the row again (the same value): jr stays statically indexed, in registers
-                    float ji;
-                    if (rl) {
-                        YrL[i] = acc;
-                        ji = JrL[i];
+                    for (int j = 0; j < ND; j++) mr[j] = c.Minv[i * D + j];
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int j = 0; j < ND; j++) acc = fmaf(mr[j], jr[j], acc);
+                    if constexpr (YB) {
+                        if (rl) YrL[i] = acc;
+                        else YrG[i] = acc;
                     } else {
-                        YrG[i] = acc;
-                        ji = JrG[i];
+                        float ji;
+                        if (rl) {
+                            YrL[i] = acc;
+                            ji = JrL[i];
+                        } else {
+                            YrG[i] = acc;
+                            ji = JrG[i];
+                        }
+                        a = fmaf(ji, acc, a);
                     }
-                    a = fmaf(ji, acc, a);
+                }
+                if constexpr (YB) {
+                    float yr[ND];
+                    if (rl) {
+#pragma unroll
+                        for (int i = 0; i < ND; i++) yr[i] = YrL[i];
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < ND; i++) yr[i] = YrG[i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < ND; i++) a = fmaf(jr[i], yr[i], a);
                 }
             }
             for (int sl = 0; sl < (PC::rc ? 0 : row_slots<ND>()); sl++) {    // RC: Y already from obj_block
@@ -442,10 +473,27 @@ HD void substep(SimCtx& c, float hdt) {
             int k = r % 3, r0 = r - k;
             const float *Jo, *Y0o;
             float a = 0.0f, b = 0.0f;           // robot-block partial sums (J_rk . Y_r0, J_rk . Y_r1), t = 0 .. D-1
+            // one block's terms of both sums: J is loaded once, and the loads of J, Y0 (and for friction row 2, Y1) are
+            // issued in batches ahead of the two chains, a over t ascending, then b over t ascending (the rolled loops'
+            // order). Statically indexed, in registers; each caller keeps its own address space
+            auto bdot = [&](const float* J, const float* Y0, const float* Y1, auto n_tag) {
+                constexpr int NT = decltype(n_tag)::value;
+                float j[NT], y[NT];
+#pragma unroll
+                for (int t = 0; t < NT; t++) j[t] = J[t];
+#pragma unroll
+                for (int t = 0; t < NT; t++) y[t] = Y0[t];
+#pragma unroll
+                for (int t = 0; t < NT; t++) a = fmaf(j[t], y[t], a);
+                if (k == 2) {
+#pragma unroll
+                    for (int t = 0; t < NT; t++) y[t] = Y1[t];
+#pragma unroll
+                    for (int t = 0; t < NT; t++) b = fmaf(j[t], y[t], b);
+                }
+            };
             auto rdot = [&](const float* Jr, const float* Y0r, const float* Y1r) {
-                for (int t = 0; t < D; t++) a = fmaf(Jr[t], Y0r[t], a);
-                if (k == 2)
-                    for (int t = 0; t < D; t++) b = fmaf(Jr[t], Y1r[t], b);
+                bdot(Jr, Y0r, Y1r, std::integral_constant<int, ND>{});       // D = ND
             };
             float jo_rc[PC::rc ? OW : 1], y0_rc[PC::rc ? 2 * OW : 1];     // RC: J of this row, Y of rows r0, r0 + 1
             if constexpr (PC::split) {
@@ -490,12 +538,9 @@ HD void substep(SimCtx& c, float hdt) {
                 Y0o = gY + (r0 - RPC) * RSN + D;
             }
             const float* Y1o = Y0o + (PC::split ? OW : RSN);
-            for (int t = 0; t < RSN - D; t++) a = fmaf(Jo[t], Y0o[t], a);
+            bdot(Jo, Y0o, Y1o, std::integral_constant<int, RSN - ND>{});
             ca0_ = a;
-            if (k == 2) {
-                for (int t = 0; t < RSN - D; t++) b = fmaf(Jo[t], Y1o[t], b);
-                ca1_ = b;
-            }
+            if (k == 2) ca1_ = b;
         }
         if (NCH == 1 || (PC::ovf && ch == 0)) {
             kca0 = ca0_; kca1 = ca1_;

@@ -181,7 +181,7 @@ __device__ void snapshot_from_tensors(SimCtx& c, const ha_state_t& st, int env, 
 
 // always inlined: as an outlined call (the inliner's choice once it grows past its threshold) the step runs
 // ~40% slower (call ABI: stack spills, no cross-phase register allocation)
-template <class PC, bool SETS3 = true>
+template <class PC, bool SETS3 = true, bool YBATCH = true>
 // n_calls gym.simulate calls. An applied object force (ha_state_t.object_force for ha_simulate, the tasks' random
 // forces) lasts one call: apply_rigid_body_force_tensors acts on the next simulate (the oracle's simulate_env alike)
 __device__ __forceinline__ void run_physics(SimCtx& c, int n_calls) {
@@ -189,7 +189,7 @@ __device__ __forceinline__ void run_physics(SimCtx& c, int n_calls) {
     for (int k = 0; k < n_calls; k++) {
         for (int sub = 0; sub < c.p->substeps; sub++) {
             c.last = k == n_calls - 1 && sub == c.p->substeps - 1;
-            substep<PC, SETS3>(c, hdt);
+            substep<PC, SETS3, YBATCH>(c, hdt);
         }
         if (c.lane < c.NO) {
             c.o[c.lane].ofx[0] = c.o[c.lane].ofx[1] = c.o[c.lane].ofx[2] = 0.0f;
@@ -450,7 +450,7 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
     if (MODE == MODE_SIMULATE) {
         // ak_simulate_kernel keeps the PGS copy loop: the three row sets cost it 16 B/lane of scratch (20 -> 36; the
         // fused step kernel, which the tasks run, stays at 28 with them)
-        run_physics<PC, TASK != HA_TASK_ALLEGRO_KUKA>(c, n_calls);
+        run_physics<PC, TASK != HA_TASK_ALLEGRO_KUKA, F::rows_y_batch>(c, n_calls);
         after_physics(c, env);
         store_env(c, S, env);
         return;
@@ -473,7 +473,7 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
         ak_controller(c, S, env);
         ak_forces(c, S, env, flags, tsv);
         if (c.lane < AK_TS_KP) tsg[c.lane] = tsv;
-        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC>(c, c.p->control_freq_inv);   // vec_task.py:409-412
+        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC, true, F::rows_y_batch>(c, c.p->control_freq_inv);   // vec_task.py:409-412
         after_physics(c, env);
         store_env(c, S, env);
         if (c.lane == 0) S.progress_buf[env] = S.progress_buf[env] + 1;                // allegro_kuka_base.py:1429
@@ -497,7 +497,7 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
         ah_controller(c, S, env);
         ah_forces(c, S, env, flags, tsv);
         if (tsg && c.lane < AH_TS_N) tsg[c.lane] = tsv;
-        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC>(c, c.p->control_freq_inv);   // vec_task.py:409-412
+        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC, true, F::rows_y_batch>(c, c.p->control_freq_inv);   // vec_task.py:409-412
         after_physics(c, env);
         store_env(c, S, env);
         if (c.lane == 0) S.progress_buf[env] = S.progress_buf[env] + 1;                // allegro_hand.py:629
@@ -507,7 +507,7 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
     }
     if (MODE == MODE_RESET) {
         task_reset(c, S, env, flags);
-        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC>(c, 1);
+        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC, true, F::rows_y_batch>(c, 1);
         after_physics(c, env);
         task_reset_finish(c, S, env);
         store_env(c, S, env);
@@ -522,7 +522,7 @@ __device__ __forceinline__ void env_body(const ha_model_t* __restrict__ model, c
     // equivalent. Phase 1: the control_freq_inv physics calls (vec_task.py:409-412). One call site keeps
     // a single copy of the physics code.
     for (int ph = do_reset ? 0 : 1; ph < 2; ph++) {
-        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC>(c, ph == 0 ? 1 : c.p->control_freq_inv);
+        if (!(flags & HA_FLAG_NO_PHYSICS)) run_physics<PC, true, F::rows_y_batch>(c, ph == 0 ? 1 : c.p->control_freq_inv);
         after_physics(c, env);
         if (ph == 0) task_reset_finish(c, S, env);
     }
