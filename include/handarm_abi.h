@@ -38,6 +38,8 @@
  *   ha_gather_obs                  compute_observations' torch.cat for a custom observation list
  *                                  (observable_vec_task.py:183-203)
  *   ha_render_camera               render_all_camera_sensors + camera image refresh (utils/camera.py:278-311)
+ *   ha_render_camera_mounted       gym.attach_camera_to_body (FOLLOW_TRANSFORM / FOLLOW_POSITION) for every env at once +
+ *                                  the same render and refresh: the camera rides on a rigid body, one pose per env
  *   ha_refresh_kinematics          gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor + refresh_jacobian_tensors /
  *                                  refresh_mass_matrix_tensors (Isaac Gym tensor API; the hand_arm tasks do not call
  *                                  them, Cartesian arm controllers written against that API do)
@@ -568,6 +570,18 @@ typedef struct ha_camera_t {
     uint32_t rng_counter;       /* per-call counter of the random subset when more than P points are on the target */
 } ha_camera_t;
 
+/* Additive v16 extension (no struct above changes, HA_ABI_VERSION stays 16): a camera mounted on a rigid body, one
+ * pose per env, computed by the launch itself (ha_render_camera_mounted).
+ * no Isaac Gym tensor counterpart: gym.attach_camera_to_body(cam, env, body, transform, mode) for every env at once */
+#define HA_CAM_FOLLOW_TRANSFORM 0   /* camera pose = body pose x mount (position and orientation follow) */
+#define HA_CAM_FOLLOW_POSITION  1   /* position = body position + mount pos (env axes); orientation = mount quat */
+typedef struct ha_camera_mount_t {
+    int32_t body;        /* row of rigid_body_state within the env, 0 <= body < B */
+    int32_t mode;        /* HA_CAM_FOLLOW_* */
+    float pos[3], quat[4];   /* mount transform (xyzw): camera frame in the body frame */
+    float* pose_out;     /* [N][7] optional: the camera pose the launch used, env frame, unit quaternion */
+} ha_camera_mount_t;
+
 /* Additive v16 extension (no struct above changes, HA_ABI_VERSION stays 16): replayed domain-randomization draws.
  * With HA_FLAG_REPLAY_DR on a step / step_io / reset / observe launch, every DR sample comes from these caller-owned
  * device buffers instead of the counter hash, so a host that draws like the reference (handarm_hip/ref_rng.py DrDraws)
@@ -748,6 +762,17 @@ int ha_gather_obs(ha_handle h, const float* const* sources, const int32_t* strid
  * view_inv: the inverse view matrix (row-vector convention, 16 floats, host memory) the point cloud uses, as
  * camera.py:68 multiplies by view_mat.inverse(). Ur5Sih task only. */
 int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv, uint32_t flags, void* stream);
+/* The same images from a camera mounted on a body (see ha_camera_mount_t), every env from its own pose, in one launch:
+ *   follow transform: q = normalize(q_body x mount quat), p = p_body + rot(q_body, mount pos)
+ *   follow position:  q = normalize(mount quat),          p = p_body + mount pos
+ * The body pose is read by the kernel from the bound rigid_body_state, the rows the link hulls' poses come from, so the
+ * camera and the geometry it sees belong to the same refresh (no host read-back, no second launch). cam->pos and
+ * cam->quat are ignored; every other field of ha_camera_t, HA_CAM_FROM_DEPTH and target_pc mean what they mean for
+ * ha_render_camera. The point cloud uses the rigid inverse of the view built from that pose. ha_render_camera's
+ * argument checks apply (but for view_inv); HA_E_ARG also for a null mount, body outside 0..B-1, an unknown mode and
+ * a zero mount quat. Ur5Sih task only. */
+int ha_render_camera_mounted(ha_handle h, const ha_camera_t* cam, const ha_camera_mount_t* mount, uint32_t flags,
+                             void* stream);
 /* Jacobian and mass-matrix tensors (see ha_kinematics_t) for all envs in one launch on `stream`, from the dof_state
  * bound with ha_bind_state: gym.refresh_jacobian_tensors / refresh_mass_matrix_tensors. HA_E_ARG for a null handle or
  * struct, for both outputs null, or for n_links outside 1..HA_MAX_LINKS when links is given; HA_E_STATE before

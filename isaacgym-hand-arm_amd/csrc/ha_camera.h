@@ -14,6 +14,10 @@
 // Launch: grid (pixel tiles of 256, envs). The env's hull poses and world bounding spheres are staged in LDS once
 // per workgroup; each thread casts one ray: a sphere test per hull (front-to-back pruned), then the plane slab of
 // the hull in its own frame (local planes read from the model, L1/L2-resident).
+//
+// Two entry points share one body (cam_render<MOUNTED>): ha_camera_kernel renders every env from the one pose of its
+// launch arguments, ha_camera_mounted_kernel from a camera mounted on a rigid body, one pose per env (Isaac Gym's
+// attach_camera_to_body), composed by the kernel from the env's row of rigid_body_state.
 #pragma once
 #include "ha_task.h"
 #include "ha_cam_hulls.h"   /* HA_CAM_MAX_HULLS and the host's worst-case count of hl[] entries */
@@ -38,12 +42,69 @@ struct CamHullLDS {
     int hull, seg, pad0, pad1;
 };
 
+// A camera mounted on a body (ha_render_camera_mounted): the fixed camera's launch plus the mount. L.cam.pos / quat,
+// L.R and L.vinv are not read; every workgroup builds its env's frame from the body's row of rigid_body_state.
+struct CamMountLaunch {
+    CamLaunch L;
+    ha_camera_mount_t mount;
+};
+
 __device__ __forceinline__ f3 cam_qrot(const float* q, f3 v) { return qrot(qf{q[0], q[1], q[2], q[3]}, v); }
 
-extern "C" __global__ void __launch_bounds__(256) ha_camera_kernel(CamLaunch L) {
+// a wave-uniform float held in an SGPR, as the fixed camera's launch arguments are
+__device__ __forceinline__ float cam_uniform(float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+
+// One body for both cameras. MOUNTED = false reads the frame (origin, view axes, inverse view) from the launch
+// arguments; MOUNTED = true computes it per workgroup from the env's body row and the mount:
+//   follow transform: q = normalize(q_body x q_mount), p = p_body + rot(q_body, pos_mount)
+//   follow position:  q = normalize(q_mount),          p = p_body + pos_mount
+// then the view axes from q as ha_render_camera does on the host (camera +X forward, +Z up; view x = -Y, y = Z,
+// z = -X), and the rigid inverse view: its rows are the view axes, its last row is p. Every thread computes the same
+// ~60 flops (the body row is one uniform address) and the twelve results are moved to SGPRs, so the ray-hull loop
+// holds what the fixed camera's holds: no LDS, no barrier of its own.
+template <bool MOUNTED>
+__device__ __forceinline__ void cam_render(const CamLaunch& L, const ha_camera_mount_t* M) {
     __shared__ CamHullLDS hl[HA_CAM_MAX_HULLS];
     const int env = blockIdx.y;
     const ha_camera_t& cam = L.cam;
+    float R[9], po[3], vi[12];      // MOUNTED: view axes, camera origin, rows 0-3 of the inverse view (3 columns each)
+    if constexpr (MOUNTED) {
+        const float* r = L.body + ((size_t)env * L.B + M->body) * 13;
+        const qf qb = qf{r[3], r[4], r[5], r[6]};
+        const qf qm = qf{M->quat[0], M->quat[1], M->quat[2], M->quat[3]};
+        const bool follow = M->mode == HA_CAM_FOLLOW_TRANSFORM;
+        const qf q = qnormalize(follow ? qmul(qb, qm) : qm);
+        const f3 pm = ld3(M->pos);
+        const f3 p = ld3(r) + (follow ? qrot(qb, pm) : pm);
+        if (M->pose_out && blockIdx.x == 0 && threadIdx.x == 0) {
+            float* po7 = M->pose_out + (size_t)env * 7;
+            po7[0] = p.x; po7[1] = p.y; po7[2] = p.z;
+            po7[3] = q.x; po7[4] = q.y; po7[5] = q.z; po7[6] = q.w;
+        }
+        const float x = q.x, y = q.y, z = q.z, w = q.w;
+        const float Rc[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                             2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                             2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)};
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            R[3 * a + 0] = cam_uniform(-Rc[3 * a + 1]);
+            R[3 * a + 1] = cam_uniform(Rc[3 * a + 2]);
+            R[3 * a + 2] = cam_uniform(-Rc[3 * a + 0]);
+        }
+        po[0] = cam_uniform(p.x); po[1] = cam_uniform(p.y); po[2] = cam_uniform(p.z);
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) vi[3 * i + j] = R[3 * j + i];
+#pragma unroll
+        for (int j = 0; j < 3; j++) vi[9 + j] = po[j];
+    }
+    // the frame where each camera keeps it: the fixed one reads its launch arguments where it always did
+    auto axis = [&](int k) -> float { if constexpr (MOUNTED) return R[k]; else return L.R[k]; };
+    auto origin = [&](int j) -> float { if constexpr (MOUNTED) return po[j]; else return cam.pos[j]; };
+    auto vinv = [&](int i, int j) -> float { if constexpr (MOUNTED) return vi[3 * i + j]; else return L.vinv[4 * i + j]; };
     const ha_model_t& m = *L.m;
     const int tid = threadIdx.x;
     const int W = cam.width, H = cam.height;
@@ -106,9 +167,9 @@ extern "C" __global__ void __launch_bounds__(256) ha_camera_kernel(CamLaunch L) 
         // y = -(row - H/2)/H * 2 tan(fovy/2) -- the inverse of camera.py:57-63, so a hit maps back onto its pixel
         const float xv = ((float)col - 0.5f * (float)W) / (float)W * (2.0f * L.tanx);
         const float yv = -(((float)row - 0.5f * (float)H) / (float)H) * (2.0f * L.tany);
-        const f3 o = mk3(cam.pos[0], cam.pos[1], cam.pos[2]);
-        const f3 d = mk3(L.R[0] * xv + L.R[1] * yv - L.R[2], L.R[3] * xv + L.R[4] * yv - L.R[5],
-                         L.R[6] * xv + L.R[7] * yv - L.R[8]);
+        const f3 o = mk3(origin(0), origin(1), origin(2));
+        const f3 d = mk3(axis(0) * xv + axis(1) * yv - axis(2), axis(3) * xv + axis(4) * yv - axis(5),
+                         axis(6) * xv + axis(7) * yv - axis(8));
         const float dd = dot3(d, d);
         const float inv_len = 1.0f / sqrtf(dd);
         float best = 3.0e38f;
@@ -181,12 +242,18 @@ extern "C" __global__ void __launch_bounds__(256) ha_camera_kernel(CamLaunch L) 
         float xyz[3];
 #pragma unroll
         for (int j = 0; j < 3; j++)
-            xyz[j] = ((h0 * L.vinv[0 * 4 + j] + h1 * L.vinv[1 * 4 + j]) + h2 * L.vinv[2 * 4 + j]) + L.vinv[3 * 4 + j];
+            xyz[j] = ((h0 * vinv(0, j) + h1 * vinv(1, j)) + h2 * vinv(2, j)) + vinv(3, j);
         const bool valid = depth > -cam.max_depth && xyz[0] > cam.workspace[0] && xyz[0] < cam.workspace[1] &&
                            xyz[1] > cam.workspace[2] && xyz[1] < cam.workspace[3];
         float4 v4 = make_float4(xyz[0], xyz[1], xyz[2], valid ? 1.0f : 0.0f);
         reinterpret_cast<float4*>(cam.pointcloud)[out] = v4;
     }
+}
+
+extern "C" __global__ void __launch_bounds__(256) ha_camera_kernel(CamLaunch L) { cam_render<false>(L, nullptr); }
+
+extern "C" __global__ void __launch_bounds__(256) ha_camera_mounted_kernel(CamMountLaunch ML) {
+    cam_render<true>(ML.L, &ML.mount);
 }
 
 // {camera}_target_object_pointcloud (_refresh_segmented_pointcloud, multi_object.py:837-855): the camera points

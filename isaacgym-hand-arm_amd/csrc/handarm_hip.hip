@@ -1643,8 +1643,8 @@ int ha_gather_obs(ha_handle h, const float* const* sources, const int32_t* strid
     return HA_OK;
 }
 
-int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv, uint32_t flags, void* stream) {
-    if (!h || !h->bound || !cam || !view_inv) return HA_E_ARG;
+// ha_render_camera's argument checks and the part of its launch both cameras share (everything but the frame)
+static int cam_fill_launch(ha_handle h, const ha_camera_t* cam, uint32_t flags, CamLaunch& L) {
     if (h->task != HA_TASK_UR5SIH || !h->st.object_indices || !h->st.goal_pos) return HA_E_STATE;
     if (cam->width < 1 || cam->height < 1 || (long long)cam->width * cam->height > (1 << 24) ||
         !(cam->fovx_deg > 0.0f && cam->fovx_deg < 180.0f) || !(cam->max_depth > 0.0f))
@@ -1653,7 +1653,8 @@ int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv,
     if (h->NO > HA_MAX_OBJ) return HA_E_ARG;
     // the worst-case hull table of an env (ha_cam_hull_count, from the host model at ha_create) must fit the kernel's
     if (h->cam_hulls < 0 || h->cam_hulls > HA_CAM_MAX_HULLS || h->cam_link_hulls > 256) return HA_E_MODEL;
-    CamLaunch L;
+    if (cam->target_pc && (!cam->segmentation || !cam->pointcloud || cam->target_points < 1 || !h->st.target_object_index))
+        return HA_E_ARG;
     L.cam = *cam;
     L.m = h->d_model;
     L.root = h->st.root_state;
@@ -1668,6 +1669,38 @@ int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv,
     L.body_robot0 = h->cam_body_robot0;
     L.n_link_hulls = h->cam_link_hulls;
     L.n_static = h->cam_static;
+    const float pi = 3.14159265358979f;
+    L.tanx = tanf(0.5f * cam->fovx_deg * pi / 180.0f);
+    L.tany = L.tanx * (float)cam->height / (float)cam->width;
+    L.fu = 2.0f * L.tanx;               // 2 / proj[0][0] (camera.py:317)
+    L.fv = 2.0f * L.tany;               // 2 / proj[1][1] (camera.py:318)
+    L.flags = flags;
+    return HA_OK;
+}
+
+// the target-object cloud from the images the camera launch just wrote (same stream)
+static int cam_target_launch(ha_handle h, const ha_camera_t* cam, void* stream) {
+    if (!cam->target_pc) return HA_OK;
+    CamTargetLaunch T;
+    T.pointcloud = cam->pointcloud;
+    T.segmentation = cam->segmentation;
+    T.target_index = h->st.target_object_index;
+    T.out = cam->target_pc;
+    T.N = h->N;
+    T.HW = cam->width * cam->height;
+    T.P = cam->target_points;
+    T.seed = h->h_params.seed;
+    T.counter = cam->rng_counter;
+    hipLaunchKernelGGL(ha_camera_target_kernel, dim3(h->N), dim3(256), 0, (hipStream_t)stream, T);
+    HIPCHK(hipGetLastError());
+    return HA_OK;
+}
+
+int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv, uint32_t flags, void* stream) {
+    if (!h || !h->bound || !cam || !view_inv) return HA_E_ARG;
+    CamLaunch L;
+    int rc = cam_fill_launch(h, cam, flags, L);
+    if (rc != HA_OK) return rc;
     // camera frame (Isaac Gym: +X forward, +Y left, +Z up) -> view axes (x right = -Y, y up = Z, z back = -X)
     const float* q = cam->quat;
     float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
@@ -1680,33 +1713,34 @@ int ha_render_camera(ha_handle h, const ha_camera_t* cam, const float* view_inv,
         L.R[3 * r + 1] = Rc[3 * r + 2];
         L.R[3 * r + 2] = -Rc[3 * r + 0];
     }
-    const float pi = 3.14159265358979f;
-    L.tanx = tanf(0.5f * cam->fovx_deg * pi / 180.0f);
-    L.tany = L.tanx * (float)cam->height / (float)cam->width;
-    L.fu = 2.0f * L.tanx;               // 2 / proj[0][0] (camera.py:317)
-    L.fv = 2.0f * L.tany;               // 2 / proj[1][1] (camera.py:318)
     for (int k = 0; k < 16; k++) L.vinv[k] = view_inv[k];
-    L.flags = flags;
     int pixels = cam->width * cam->height;
-    if (cam->target_pc && (!cam->segmentation || !cam->pointcloud || cam->target_points < 1 || !h->st.target_object_index))
-        return HA_E_ARG;
     hipLaunchKernelGGL(ha_camera_kernel, dim3((pixels + 255) / 256, h->N), dim3(256), 0, (hipStream_t)stream, L);
     HIPCHK(hipGetLastError());
-    if (cam->target_pc) {
-        CamTargetLaunch T;
-        T.pointcloud = cam->pointcloud;
-        T.segmentation = cam->segmentation;
-        T.target_index = h->st.target_object_index;
-        T.out = cam->target_pc;
-        T.N = h->N;
-        T.HW = pixels;
-        T.P = cam->target_points;
-        T.seed = h->h_params.seed;
-        T.counter = cam->rng_counter;
-        hipLaunchKernelGGL(ha_camera_target_kernel, dim3(h->N), dim3(256), 0, (hipStream_t)stream, T);
-        HIPCHK(hipGetLastError());
-    }
-    return HA_OK;
+    return cam_target_launch(h, cam, stream);
+}
+
+int ha_render_camera_mounted(ha_handle h, const ha_camera_t* cam, const ha_camera_mount_t* mount, uint32_t flags,
+                             void* stream) {
+    if (!h || !h->bound || !cam || !mount) return HA_E_ARG;
+    CamMountLaunch ML;
+    int rc = cam_fill_launch(h, cam, flags, ML.L);
+    if (rc != HA_OK) return rc;
+    if (mount->body < 0 || mount->body >= h->B) return HA_E_ARG;
+    if (mount->mode != HA_CAM_FOLLOW_TRANSFORM && mount->mode != HA_CAM_FOLLOW_POSITION) return HA_E_ARG;
+    const float* q = mount->quat;
+    float qq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    // x - x is 0 for a finite x and NaN for an infinity or a NaN, so each comparison is false for those
+    if (!(qq > 0.0f) || !(qq - qq == 0.0f)) return HA_E_ARG;
+    for (int k = 0; k < 3; k++)
+        if (!(mount->pos[k] - mount->pos[k] == 0.0f)) return HA_E_ARG;
+    for (int k = 0; k < 9; k++) ML.L.R[k] = 0.0f;           // the frame is the kernel's: R and vinv are not read
+    for (int k = 0; k < 16; k++) ML.L.vinv[k] = 0.0f;
+    ML.mount = *mount;
+    int pixels = cam->width * cam->height;
+    hipLaunchKernelGGL(ha_camera_mounted_kernel, dim3((pixels + 255) / 256, h->N), dim3(256), 0, (hipStream_t)stream, ML);
+    HIPCHK(hipGetLastError());
+    return cam_target_launch(h, cam, stream);
 }
 
 int ha_contact_capacity(ha_handle h) { return h ? h->fi->contacts : HA_E_ARG; }

@@ -50,6 +50,7 @@ SIGNATURES = {
     "ha_pointclouds": ([H, C.POINTER(HM.HaPointcloud), S], C.c_int),
     "ha_pointcloud_times": ([H, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)], C.c_int),
     "ha_render_camera": ([H, C.POINTER(HM.HaCamera), C.POINTER(C.c_float), C.c_uint32, S], C.c_int),
+    "ha_render_camera_mounted": ([H, C.POINTER(HM.HaCamera), C.POINTER(HM.HaCameraMount), C.c_uint32, S], C.c_int),
     "ha_refresh_kinematics": ([H, C.POINTER(HM.HaKinematics), S], C.c_int),
     "ha_refresh_contacts": ([H, C.POINTER(HM.HaContacts), S], C.c_int),
     "ha_cartesian_targets": ([H, C.POINTER(HM.HaCartesian), S], C.c_int),

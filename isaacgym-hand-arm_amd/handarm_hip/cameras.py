@@ -6,6 +6,11 @@ fovx, resolution) and produces the images of ``IsaacGymCameraSensor`` (:250-333)
 (here ray cast against the collision geometry, see csrc/ha_camera.h) and the point cloud of
 ``_compute_pointcloud`` (:302-311). One kernel launch renders every env.
 
+A camera may be mounted on a rigid body (``link=`` / ``body=``; Isaac Gym's ``attach_camera_to_body`` with
+FOLLOW_TRANSFORM / FOLLOW_POSITION): ``pos`` / ``quat`` are then the mount transform in the body frame and the launch
+(``ha_render_camera_mounted``) composes every env's camera pose on the device from that env's row of
+``rigid_body_state``.
+
 Conventions (Isaac Gym's, restated): the camera looks along its local +X with +Z up; the view matrix is the
 OpenGL one in row-vector form (points as rows, ``[p, 1] @ V``), so depth is the negative view-space z; the
 projection matrix's [0][0] / [1][1] are 1 / tan(fov / 2) with square pixels. Envs are rendered in their own
@@ -62,12 +67,39 @@ def static_segmentation_ids(scene):
     return [2 if s["name"].startswith("bin") else 0 for s in statics]
 
 
+FOLLOW_MODES = {"transform": HM.CAM_FOLLOW_TRANSFORM, "position": HM.CAM_FOLLOW_POSITION}
+
+
+def mount_body(sim, link=None, body=None):
+    """The ``rigid_body_state`` row (within an env) a mounted camera follows, or None for a fixed camera. ``link``: a
+    scene link name or model link index, resolved by ``sim.link_index`` as the controllers do, row
+    ``model.body_robot0 + link``; ``body``: the row itself (an object's, say)."""
+    if link is None and body is None:
+        return None
+    if link is not None and body is not None:
+        raise ValueError("a camera is mounted on a link or on a body row, not both")
+    if link is not None:
+        i = sim.link_index(link)
+        if not 0 <= i < sim.num_links:
+            raise ValueError(f"link index {i} outside 0..{sim.num_links - 1}")
+        return int(sim.model.body_robot0) + i
+    if not 0 <= int(body) < sim.num_bodies:
+        raise ValueError(f"body row {body} outside 0..{sim.num_bodies - 1}")
+    return int(body)
+
+
 class CameraSensor:
     """One camera over every env of ``sim``. ``images[kind]`` for kind in ``outputs``: depth (N, H, W) f32,
-    segmentation (N, H, W) int32, pointcloud (N, H, W, 4) f32 - the reference's current_sensor_observation."""
+    segmentation (N, H, W) int32, pointcloud (N, H, W, 4) f32 - the reference's current_sensor_observation.
+
+    With ``link`` (scene link name or model link index) or ``body`` (a ``rigid_body_state`` row) the camera is mounted:
+    ``pos`` / ``quat`` are the camera frame in the body frame, ``follow`` is "transform" (position and orientation
+    follow the body) or "position" (position = body position + pos in env axes, orientation = quat), and ``pose``
+    holds the (N, 7) camera poses of the last render."""
 
     def __init__(self, sim, pos, quat, fovx=87, resolution=(160, 90), outputs=IMAGE_TYPES, scene=None,
-                 max_depth=MAX_DEPTH, workspace=WORKSPACE, max_num_points=128):
+                 max_depth=MAX_DEPTH, workspace=WORKSPACE, max_num_points=128, link=None, body=None,
+                 follow="transform"):
         if sim.task != HM.TASK_UR5SIH:
             raise NotImplementedError("camera sensors are built for the Ur5Sih scenes")
         for k in outputs:
@@ -76,13 +108,21 @@ class CameraSensor:
                                           "(no colour: the collision geometry has no materials)")
         if not 0 < fovx < 180:
             raise ValueError(f"Horizontal field-of-view (fovx) should be in [0, 180], but found '{fovx}'.")
+        if follow not in FOLLOW_MODES:
+            raise ValueError(f"follow {follow!r}: one of {sorted(FOLLOW_MODES)}")
         self.sim = sim
+        self.body = mount_body(sim, link, body)
+        self.follow = follow
+        if self.body is not None and not np.linalg.norm(np.asarray(quat, np.float64)) > 0:
+            raise ValueError("the mount quaternion is zero")
         self.width, self.height = int(resolution[0]), int(resolution[1])
         self.fovx = float(fovx)
         self.pos, self.quat = list(pos), list(quat)
         N, H, W = sim.num_envs, self.height, self.width
         dev = sim.device
         scene = scene if scene is not None else sim.scene
+        # a fixed camera's view; for a mounted one this is the mount transform's and the launch does not read it
+        # (view_matrices() gives the per-env ones)
         self.view = view_matrix(pos, quat)
         self.proj = projection_matrix(fovx, W, H)
         # camera.py:68 multiplies by view_mat.inverse(): the same fp32 inverse, computed once on the host
@@ -117,6 +157,16 @@ class CameraSensor:
         c.rng_counter = 0
         self.args = c
         self._vinv = (C.c_float * 16)(*self.view_inv.reshape(-1).tolist())
+        self.pose = None
+        if self.body is not None:
+            self.pose = torch.zeros((N, 7), dtype=torch.float32, device=dev)
+            self.pose[:, 6] = 1.0
+            mt = HM.HaCameraMount()
+            mt.body, mt.mode = self.body, FOLLOW_MODES[follow]
+            mt.pos[:] = [float(v) for v in pos]
+            mt.quat[:] = [float(v) for v in quat]
+            mt.pose_out = self.pose.data_ptr()
+            self.mount = mt
 
     @property
     def projection_matrix(self):
@@ -128,5 +178,26 @@ class CameraSensor:
         cloud from images["depth"] (HA_CAM_FROM_DEPTH)."""
         flags = HM.CAM_FROM_DEPTH if from_depth else 0
         self.args.rng_counter = (self.args.rng_counter + 1) & 0xFFFFFFFF     # a fresh random subset per refresh
+        if self.body is not None:
+            _lib.check(self.sim.lib.ha_render_camera_mounted(self.sim.h, C.byref(self.args), C.byref(self.mount), flags,
+                                                             self.sim._stream()), "ha_render_camera_mounted")
+            return
         _lib.check(self.sim.lib.ha_render_camera(self.sim.h, C.byref(self.args), self._vinv, flags,
                                                  self.sim._stream()), "ha_render_camera")
+
+    def view_matrices(self):
+        """(N, 4, 4) float32 view matrices of a mounted camera's last render, in the convention of ``view_matrix``
+        (Isaac Gym's get_camera_view_matrix per env), built in torch from ``pose``."""
+        if self.pose is None:
+            raise ValueError("view_matrices() is a mounted camera's; a fixed camera has .view")
+        p, q = self.pose[:, 0:3], self.pose[:, 3:7]
+        x, y, z, w = (q / q.norm(dim=1, keepdim=True)).unbind(1)
+        Rc = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                          2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                          2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], dim=1).view(-1, 3, 3)
+        Rgl = torch.stack([-Rc[:, :, 1], Rc[:, :, 2], -Rc[:, :, 0]], dim=2)     # columns: view axes in the env frame
+        V = torch.zeros((p.shape[0], 4, 4), dtype=torch.float32, device=p.device)
+        V[:, 0:3, 0:3] = Rgl
+        V[:, 3, 0:3] = -torch.einsum("ni,nij->nj", p, Rgl)
+        V[:, 3, 3] = 1.0
+        return V

@@ -295,6 +295,15 @@ class HaCamera(C.Structure):
                 ("target_pc", P), ("target_points", C.c_int32), ("rng_counter", C.c_uint32)]
 
 
+CAM_FOLLOW_TRANSFORM, CAM_FOLLOW_POSITION = 0, 1     # HA_CAM_FOLLOW_*
+
+
+class HaCameraMount(C.Structure):
+    """ha_camera_mount_t (include/handarm_abi.h, v16 extension): a camera mounted on a body (pose_out: device pointer)."""
+    _fields_ = [("body", C.c_int32), ("mode", C.c_int32), ("pos", C.c_float * 3), ("quat", C.c_float * 4),
+                ("pose_out", P)]
+
+
 def null_fields(task):
     """State buffers left NULL for a task: object_scale switches the physics to per-env scaled object
     geometry, which only AllegroKuka's cuboid family uses (bit-identical unscaled path otherwise)."""

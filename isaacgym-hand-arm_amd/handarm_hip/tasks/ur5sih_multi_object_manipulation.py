@@ -248,9 +248,12 @@ class Ur5SihMultiObjectManipulation:
                     raise NotImplementedError(f"camera observable {cam_name}_{k}: this build renders {IMAGE_TYPES}")
             if "pos" not in cam_cfg:
                 raise NotImplementedError(f"camera {cam_name}: ROS cameras are out of scope")
+            # `link:` (and `follow:`) are this build's extension: the camera rides on that robot link and pos / quat
+            # are its mount transform (gym.attach_camera_to_body); the reference's entries have neither key
             self.cameras[cam_name] = CameraSensor(self.sim, cam_cfg["pos"], cam_cfg["quat"], cam_cfg.get("fovx", 87),
                                                   cam_cfg.get("resolution", (160, 90)), kinds, self.scene,
-                                                  max_num_points=int(_get(cfg, "pointclouds.max_num_points", 128)))
+                                                  max_num_points=int(_get(cfg, "pointclouds.max_num_points", 128)),
+                                                  link=cam_cfg.get("link"), follow=cam_cfg.get("follow", "transform"))
             for k in kinds:
                 self.camera_obs[f"{cam_name}_{k}"] = (cam_name, k)
         for n in self.obs_names:
