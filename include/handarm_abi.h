@@ -47,6 +47,9 @@
  *                                  a tensor; no hand_arm call site: tactile observations, grasp diagnostics)
  *   ha_cartesian_targets           no Isaac Gym counterpart: the damped least-squares Cartesian controller its users write
  *                                  in torch on the Jacobian tensor, as one launch that writes joint position targets
+ *   ha_cartesian_multi_targets     no Isaac Gym counterpart: the same controller for a whole hand, up to HA_CART_MAX_TASKS
+ *                                  links (the flange or palm pose and the fingertip positions) stacked into one damped
+ *                                  least-squares step, in one launch
  * The fused entry points serve three tasks (ha_params_t.task): Ur5Sih (above), AllegroHand
  * (allegro_hand.py:586-633) and AllegroKuka (allegro_kuka_base.py:1355-1447).
  */
@@ -673,6 +676,36 @@ typedef struct ha_cartesian_t {
     float offset[3], damping, max_step, null_gain;
 } ha_cartesian_t;
 
+/* Additive v16 extension (no struct above changes, HA_ABI_VERSION stays 16): the Cartesian controller for several links
+ * at once (a whole hand: the flange or palm pose and the fingertip positions), from a kernel of its own
+ * (csrc/ha_cartesian_multi.h). ha_cartesian_t's semantics hold wherever they are not restated here. Per launched env:
+ *   task t         tool point p_t = p_link + R_link offset, error e_t (HA_CART_POSE from goal row t, HA_CART_DELTA = goal
+ *                  row t) and the 6 x D tool Jacobian J_t over (the link's ancestor-or-self DOFs) & dof_mask, as
+ *                  ha_cartesian_targets computes them
+ *   rows           a position_only task contributes rows 0..2 only (its goal quaternion / angular part is not read,
+ *                  err_out[env][t][3:6] = 0), every other task 6 rows; rows are stacked in task order, task t's scaled by
+ *                  weight: Jw = diag(w) J, ew = diag(w) e, R = the number of rows <= HA_CART_MAX_ROWS
+ *   step           dq = Jw^T (Jw Jw^T + damping^2 I_R)^-1 ew; the R x R system is formed, factored and solved in float64
+ *   null_gain > 0  dq += z - Jw^T (Jw Jw^T + damping^2 I)^-1 Jw z, z_d = null_gain (q_rest[d] - q_d) on U, the union of
+ *                  the tasks' selected DOF sets (the damped projector, with ha_cartesian_t's leak caveat)
+ *   max_step > 0   scales the whole dq; then targets[env][d] = clamp(q_d + dq_d, dof_lower[d], dof_upper[d]) for d in U.
+ *                  Nothing else in targets is written.
+ * Two tasks may name the same link with different offsets. */
+#define HA_CART_MAX_TASKS 6
+#define HA_CART_MAX_ROWS  24
+typedef struct ha_cart_task_t { int32_t link, position_only; float offset[3], weight; } ha_cart_task_t;
+typedef struct ha_cartesian_multi_t {
+    const float* goal;       /* device [n][T][7] (HA_CART_POSE) or [n][T][6] (HA_CART_DELTA); row k for the k-th listed env */
+    float* targets;          /* device [N][D] */
+    float* err_out;          /* device [N][T][6] or NULL: each task's UNWEIGHTED e */
+    const float* q_rest;     /* device [D] or NULL */
+    const int32_t* env_ids;  /* device or NULL */
+    int32_t n_envs, n_tasks, mode;
+    uint32_t dof_mask;
+    float damping, max_step, null_gain;
+    ha_cart_task_t task[HA_CART_MAX_TASKS];
+} ha_cartesian_multi_t;
+
 typedef struct ha_handle_s* ha_handle;
 
 int ha_abi_version(void);
@@ -790,6 +823,13 @@ int ha_refresh_contacts(ha_handle h, const ha_contacts_t* c, void* stream);
  * negative or not finite, null_gain > 0 with q_rest null, a dof_mask without an ancestor-or-self DOF of link, or env_ids
  * with n_envs < 1; HA_E_STATE before ha_bind_state. */
 int ha_cartesian_targets(ha_handle h, const ha_cartesian_t* c, void* stream);
+/* One stacked damped least-squares step for several links (see ha_cartesian_multi_t) in one launch on `stream`, one
+ * wavefront per env or per listed env; the launch reads the bound dof_state and writes targets and err_out only. HA_E_ARG,
+ * checked before any HIP call: a null handle, struct, goal or targets; n_tasks outside 1..HA_CART_MAX_TASKS; a task link
+ * outside 1..L-1; more than HA_CART_MAX_ROWS rows; a weight that is not finite and > 0; a task none of whose
+ * ancestor-or-self DOFs is in dof_mask; and ha_cartesian_targets' checks of mode, damping, max_step, null_gain, q_rest
+ * and env_ids. HA_E_STATE before ha_bind_state. */
+int ha_cartesian_multi_targets(ha_handle h, const ha_cartesian_multi_t* c, void* stream);
 
 #ifdef __cplusplus
 }

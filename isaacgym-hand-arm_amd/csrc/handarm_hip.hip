@@ -14,6 +14,7 @@
 #include "ha_camera.h"
 #include "ha_kinematics.h"
 #include "ha_cartesian.h"
+#include "ha_cartesian_multi.h"
 #include "ha_family.h"   /* Family<FAM>: every per-family constant; FamPhys<FAM>, pair_slots */
 
 enum { MODE_SIMULATE = 0, MODE_STEP = 1, MODE_OBSERVE = 2, MODE_RESET = 3 };
@@ -1615,6 +1616,62 @@ int ha_cartesian_targets(ha_handle h, const ha_cartesian_t* c, void* stream) {
     a.null_gain = c->null_gain;
     hipLaunchKernelGGL(ha_cartesian_kernel, dim3((a.n + HA_KIN_WAVES - 1) / HA_KIN_WAVES), dim3(64 * HA_KIN_WAVES), 0,
                        (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
+    return HA_OK;
+}
+
+// One stacked damped least-squares step for several links (ha_cartesian_multi.h): one wavefront per env, or per listed
+// env. Identity order or the caller's list, no timing record. Everything the kernel needs of the model per task (DOF
+// chain, path, depth, first row) is resolved here, and every refusal comes before the first HIP call
+int ha_cartesian_multi_targets(ha_handle h, const ha_cartesian_multi_t* c, void* stream) {
+    if (!h || !c || !c->goal || !c->targets) return HA_E_ARG;
+    if (c->n_tasks < 1 || c->n_tasks > HA_CART_MAX_TASKS) return HA_E_ARG;
+    if (c->mode != HA_CART_POSE && c->mode != HA_CART_DELTA) return HA_E_ARG;
+    // x - x is 0 for a finite x and NaN for an infinity or a NaN, so each comparison is false for those
+    if (!(c->damping - c->damping == 0.0f && c->damping > 0.0f)) return HA_E_ARG;
+    if (!(c->max_step - c->max_step == 0.0f && c->max_step >= 0.0f)) return HA_E_ARG;
+    if (!(c->null_gain - c->null_gain == 0.0f && c->null_gain >= 0.0f)) return HA_E_ARG;
+    if (c->null_gain > 0.0f && !c->q_rest) return HA_E_ARG;
+    if (c->env_ids && c->n_envs < 1) return HA_E_ARG;
+    CartMultiLaunch a;
+    a.R = 0;
+    a.depth = 0;
+    a.path = a.dofs = 0u;
+    for (int t = 0; t < HA_CART_MAX_TASKS; t++) {
+        const ha_cart_task_t& k = c->task[t < c->n_tasks ? t : 0];
+        if (k.link < 1 || k.link >= h->L) return HA_E_ARG;
+        if (!(k.weight - k.weight == 0.0f && k.weight > 0.0f)) return HA_E_ARG;
+        if (!(h->link_dofs[k.link] & c->dof_mask)) return HA_E_ARG;
+        a.link[t] = k.link;
+        a.row0[t] = a.R;
+        a.nrow[t] = k.position_only ? 3 : 6;
+        a.tdofs[t] = h->link_dofs[k.link] & c->dof_mask;
+        for (int i = 0; i < 3; i++) a.off[t][i] = k.offset[i];
+        a.w[t] = k.weight;
+        if (t >= c->n_tasks) continue;         // the spare slots repeat task 0 and are never read
+        a.R += a.nrow[t];
+        a.path |= h->link_path[k.link];
+        a.dofs |= a.tdofs[t];
+        if (h->link_depth[k.link] > a.depth) a.depth = h->link_depth[k.link];
+    }
+    if (a.R > HA_CART_MAX_ROWS) return HA_E_ARG;
+    if (!h->bound) return HA_E_STATE;
+    a.model = h->d_model;
+    a.dof_state = h->st.dof_state;
+    a.goal = c->goal;
+    a.targets = c->targets;
+    a.err_out = c->err_out;
+    a.q_rest = c->null_gain > 0.0f ? c->q_rest : nullptr;
+    a.env_ids = c->env_ids;
+    a.lam2 = (double)c->damping * (double)c->damping;
+    a.N = h->N;
+    a.n = c->env_ids ? c->n_envs : h->N;
+    a.T = c->n_tasks;
+    a.mode = c->mode;
+    a.max_step = c->max_step;
+    a.null_gain = c->null_gain;
+    hipLaunchKernelGGL(ha_cartesian_multi_kernel, dim3((a.n + HA_KIN_WAVES - 1) / HA_KIN_WAVES), dim3(64 * HA_KIN_WAVES),
+                       0, (hipStream_t)stream, a);
     HIPCHK(hipGetLastError());
     return HA_OK;
 }

@@ -54,11 +54,14 @@ SIGNATURES = {
     "ha_refresh_kinematics": ([H, C.POINTER(HM.HaKinematics), S], C.c_int),
     "ha_refresh_contacts": ([H, C.POINTER(HM.HaContacts), S], C.c_int),
     "ha_cartesian_targets": ([H, C.POINTER(HM.HaCartesian), S], C.c_int),
+    "ha_cartesian_multi_targets": ([H, C.POINTER(HM.HaCartesianMulti), S], C.c_int),
     "ha_gather_obs": ([H, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, fp, C.c_int32, fp, S], C.c_int),
 }
 
 
 HaCartesian = HM.HaCartesian     # the ctypes mirrors of the ABI structs live in model.py
+HaCartTask = HM.HaCartTask
+HaCartesianMulti = HM.HaCartesianMulti
 
 
 class HandArmError(RuntimeError):

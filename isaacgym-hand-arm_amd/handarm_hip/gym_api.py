@@ -145,7 +145,9 @@ class Gym:
     def set_cartesian_pose_target(self, sim, controller, goal):
         """Isaac Gym has no counterpart: one step of a handarm_hip.controllers.CartesianController of this sim (one
         launch that writes the joint position targets the next gym.simulate drives to), here so that code written
-        against this namespace need not leave it. goal: (N, 7) pos + quat xyzw, or (N, 6) in "delta" mode."""
+        against this namespace need not leave it. goal: (N, 7) pos + quat xyzw, or (N, 6) in "delta" mode. A
+        controllers.WholeHandController is driven the same way (only ``.sim`` and ``.step`` are used): goal is then
+        (N, T, 7) or (N, T, 6), row t for its task t."""
         if controller.sim is not sim:
             raise ValueError("the controller belongs to another sim")
         controller.step(_t(goal))

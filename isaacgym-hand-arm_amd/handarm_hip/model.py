@@ -284,6 +284,22 @@ class HaCartesian(C.Structure):
                 ("offset", C.c_float * 3), ("damping", C.c_float), ("max_step", C.c_float), ("null_gain", C.c_float)]
 
 
+CART_MAX_TASKS, CART_MAX_ROWS = 6, 24     # HA_CART_MAX_TASKS / HA_CART_MAX_ROWS
+
+
+class HaCartTask(C.Structure):
+    """ha_cart_task_t (include/handarm_abi.h, v16 extension): one link of a whole-hand Cartesian launch."""
+    _fields_ = [("link", C.c_int32), ("position_only", C.c_int32), ("offset", C.c_float * 3), ("weight", C.c_float)]
+
+
+class HaCartesianMulti(C.Structure):
+    """ha_cartesian_multi_t (include/handarm_abi.h, v16 extension): one launch of the whole-hand Cartesian controller
+    (device pointers)."""
+    _fields_ = [("goal", P), ("targets", P), ("err_out", P), ("q_rest", P), ("env_ids", P), ("n_envs", C.c_int32),
+                ("n_tasks", C.c_int32), ("mode", C.c_int32), ("dof_mask", C.c_uint32), ("damping", C.c_float),
+                ("max_step", C.c_float), ("null_gain", C.c_float), ("task", HaCartTask * CART_MAX_TASKS)]
+
+
 CAM_FROM_DEPTH = 1
 
 

@@ -347,6 +347,89 @@ class HandArmSim:
         self._cart_hold = (goal, q_rest, ids)
         return targets
 
+    def cartesian_tasks(self, tasks, dofs=None):
+        """``(HaCartTask array, n_tasks, dof_mask)`` of a whole-hand task list, checked: every refusal the library
+        would make for the list is a HandArmError here, before any launch. tasks: dicts with ``link`` (index or scene
+        link name) and optionally ``offset`` (3 floats, default 0), ``position_only`` (default False) and ``weight``
+        (default 1)."""
+        tasks = list(tasks)
+        if not 1 <= len(tasks) <= HM.CART_MAX_TASKS:
+            raise _lib.HandArmError(f"{len(tasks)} tasks: a launch takes 1..{HM.CART_MAX_TASKS}")
+        mask = 0
+        for d in (range(self.num_dofs) if dofs is None else dofs):
+            if not 0 <= int(d) < self.num_dofs:
+                raise _lib.HandArmError(f"DOF index {d} outside 0..{self.num_dofs - 1}")
+            mask |= 1 << int(d)
+        arr, rows = (HM.HaCartTask * HM.CART_MAX_TASKS)(), 0
+        for t, task in enumerate(tasks):
+            unknown = set(task) - {"link", "offset", "position_only", "weight"}
+            if unknown or "link" not in task:
+                raise _lib.HandArmError(f"task {t}: keys are link, offset, position_only, weight; got {sorted(task)}")
+            try:
+                li = self.link_index(task["link"])
+            except KeyError as e:
+                raise _lib.HandArmError(f"task {t}: {e.args[0]}") from None
+            if not 1 <= li < self.num_links:
+                raise _lib.HandArmError(f"task {t}: link index {li} outside 1..{self.num_links - 1}")
+            w = float(task.get("weight", 1.0))
+            if not (w > 0.0 and w != float("inf")):
+                raise _lib.HandArmError(f"task {t}: weight {w} is not finite and > 0")
+            if not any(mask >> d & 1 for d in self.link_dofs(li)):
+                raise _lib.HandArmError(f"task {t}: none of the selected DOFs moves link {li}")
+            ponly = bool(task.get("position_only", False))
+            rows += 3 if ponly else 6
+            arr[t] = HM.HaCartTask(li, int(ponly), (C.c_float * 3)(*[float(v) for v in task.get("offset", (0, 0, 0))]),
+                                   w)
+        if rows > HM.CART_MAX_ROWS:
+            raise _lib.HandArmError(f"the tasks stack {rows} rows: a launch takes at most {HM.CART_MAX_ROWS}")
+        return arr, len(tasks), mask
+
+    def cartesian_multi_targets(self, goal, tasks, dofs=None, mode="pose", damping=0.05, max_step=0.0, q_rest=None,
+                                null_gain=0.0, targets=None, err_out=None, env_ids=None):
+        """One damped least-squares step for several links at once (a whole hand: the flange or palm pose and the
+        fingertip positions), in one launch on the current stream and without a host sync (ha_cartesian_multi_targets;
+        no Isaac Gym counterpart). tasks: a list of up to 6 dicts, ``link`` (index or scene link name), ``offset``,
+        ``position_only``, ``weight``; a position-only task stacks 3 rows, every other 6, at most 24 in all. The rows are
+        scaled by their task's weight and solved together, the R x R system in float64:
+        ``targets[env, d] = clamp(q + Jw^T (Jw Jw^T + damping^2 I)^-1 ew, lower, upper)`` on the union of the tasks'
+        ancestor DOFs within ``dofs`` (DOF indices, default all), every other element of ``targets`` untouched.
+        goal: float32 device tensor (n, T, 7) tool poses (mode "pose"; a position-only task's quaternion is not read)
+        or (n, T, 6) task errors (mode "delta"), n = num_envs or len(env_ids). max_step, q_rest / null_gain, targets and
+        env_ids as cartesian_targets; err_out (N, T, 6) receives each task's unweighted error. Returns targets."""
+        if isinstance(mode, str):
+            if mode not in ("pose", "delta"):
+                raise _lib.HandArmError(f"mode must be 'pose' or 'delta', not {mode!r}")
+            mode = HM.CART_POSE if mode == "pose" else HM.CART_DELTA
+        mode = int(mode)                   # HM.CART_*: the library checks the value
+        arr, T, mask = self.cartesian_tasks(tasks, dofs)
+        ids = None if env_ids is None else env_ids.to(device=self.device, dtype=torch.int32).contiguous()
+        n = self.num_envs if ids is None else int(ids.numel())
+        if n < 1:
+            raise _lib.HandArmError("env_ids is empty")
+        width = 6 if mode == HM.CART_DELTA else 7
+
+        def dev(x, shape, what):
+            if x is None:
+                return None
+            x = torch.as_tensor(x, dtype=torch.float32, device=self.device)
+            if tuple(x.shape) != shape or not x.is_contiguous():
+                raise _lib.HandArmError(f"{what} must be a contiguous float32 tensor of shape {shape}")
+            return x
+        goal = dev(goal, (n, T, width), "goal")
+        targets = dev(self.t["sim_targets"] if targets is None else targets, (self.num_envs, self.num_dofs), "targets")
+        err_out = dev(err_out, (self.num_envs, T, 6), "err_out")
+        q_rest = dev(q_rest, (self.num_dofs,), "q_rest")
+        c = HM.HaCartesianMulti(goal.data_ptr() if goal is not None else None, targets.data_ptr(),
+                                err_out.data_ptr() if err_out is not None else None,
+                                q_rest.data_ptr() if q_rest is not None else None,
+                                ids.data_ptr() if ids is not None else None, n if ids is not None else 0, T, mode,
+                                mask, float(damping), float(max_step), float(null_gain), arr)
+        _lib.check(self.lib.ha_cartesian_multi_targets(self.h, C.byref(c), self._stream()),
+                   "ha_cartesian_multi_targets")
+        # the launch reads these asynchronously: hold them until the next call replaces them
+        self._cart_multi_hold = (goal, q_rest, ids)
+        return targets
+
     def simulate(self, n_calls=1, flags=0, env_ids=None):
         """gym.simulate n_calls times; env_ids (device tensor of distinct env indices): those envs only."""
         if env_ids is None:
